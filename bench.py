@@ -9,6 +9,16 @@ schedule (device radix sort into 4-pair wave groups) -> fp32 forward kernel ->
 fp64 rescue kernel.  `value` = total cells (sum of R*H) of all ranks * steps /
 max-over-ranks wall time, in GCUPS.
 
+A plain run (`--gpus 1 --steps N --warmup W`) does only what that headline
+needs: it synthesises the batch, warms up, times the N steps and prints the
+line (headline, stage times and the roofline figures derived from those same
+steps).  `--dump-outputs DIR` also writes what the last timed step computed
+(the log10 likelihood of every pair) as .npy files; with the same arguments
+the inputs are the same from run to run.  Everything below (the SW legs, the
+CPU baselines and parity blocks, the end-to-end commands, C4 / C5) runs only
+with `--full`, where --no-bsw / --no-cpu-baseline / --no-e2e / --no-c4 still
+switch single legs off.
+
 Multi-GPU: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set)
 this process is one rank; `--gpus N` without WORLD_SIZE starts the N rank
 processes itself (fresh children, before this parent touches the GPU) and
@@ -18,14 +28,14 @@ torch.distributed carries only the barrier and the max-over-ranks timing
 reduction.  `--dry-run` runs the same rank/launcher/reduction path on CPU
 (gloo) with a stand-in workload, for the CPU tests.
 
-C4 / C5 (configs[3], configs[4]) as the reference runs them: ONE `fcs-genome
-htc` job and ONE `fcs-genome mutect2` job over a chr1-sized genome (--c4-mbp,
+With --full, C4 / C5 (configs[3], configs[4]) as the reference runs them: ONE
+`fcs-genome htc` job and ONE `fcs-genome mutect2` job over a chr1-sized genome (--c4-mbp,
 248 Mbp, the same at every N), their 32 interval shards dealt over all N GPUs
 of the node; at N = 1 beside each job's CPU PairHMM path.  The line ends with
 `summary`, every headline figure in one short block.
 
-Also reported (not the headline): banded-SW ksw_extend2 GCUPS on C3-shaped
-synthetic extension tasks (2x151 bp reads, bwa defaults) and on the fixed
+Also reported with --full (not the headline): banded-SW ksw_extend2 GCUPS on
+C3-shaped synthetic extension tasks (2x151 bp reads, bwa defaults) and on the fixed
 qlen=151/tlen=251 variant, cells counted by the kernel exactly as ksw_extend2
 evaluates them; and the CPU baseline (the oracle restatement, OpenMP) on a
 bounded sample, rank 0 / N=1 only.
@@ -1142,6 +1152,27 @@ def load_fcship():
     return fcship
 
 
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs: all files of one rank together
+
+
+def dump_outputs(out_dir, rank, arrays):
+    """--dump-outputs: the arrays the timed path returned in its last step, as
+    out_dir/<name>.npy (rank 0; `<name>.rank<r>.npy` for the other ranks) in
+    float32 or float64.  An array over its share of DUMP_BYTES_MAX is written
+    as a fixed sample: the elements at a seeded, sorted choice of indices,
+    the same from run to run for the same shape."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES_MAX // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + (f".rank{rank}" if rank else "") + ".npy"), np.ascontiguousarray(a))
+
+
 def dry_step(args):
     """CPU stand-in for the PairHMM pass in --dry-run: a fixed amount of numpy work."""
     a = np.random.default_rng(args.seed).random((256, 256))
@@ -1161,22 +1192,32 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--pairs", type=int, default=1_000_000)
     ap.add_argument("--seed", type=int, default=20261015)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the SW legs, the CPU baselines and parity blocks, the "
+                         "end-to-end commands and C4 / C5 (the --no-* options below switch single legs off)")
     ap.add_argument("--bsw-reads", type=int, default=500_000)
-    ap.add_argument("--no-bsw", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-bsw", action="store_true", help="with --full: skip the SW legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip CPU baselines and parity")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
-    ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the end-to-end commands")
     ap.add_argument("--e2e-mbp", type=float, default=31.0,
                     help="per-GPU genome of the htc / mutect2 runs (31 Mbp = chr1 / 8 GPUs, the C4 share)")
     ap.add_argument("--e2e-align-mbp", type=float, default=4.0, help="genome of the align run")
     ap.add_argument("--e2e-reps", type=int, default=3,
                     help="runs of each e2e command; the fastest is reported, every run's wall time listed")
     ap.add_argument("--no-c4", action="store_true",
-                    help="skip the C4 / C5 legs (one htc and one mutect2 job over --c4-mbp, dealt to all N GPUs)")
+                    help="with --full: skip the C4 / C5 legs (one htc and one mutect2 job over --c4-mbp, dealt to all "
+                         "N GPUs)")
     ap.add_argument("--c4-mbp", type=float, default=248.0,
                     help="genome of the C4 / C5 jobs (248 Mbp = chr1), the same at every N")
     ap.add_argument("--c4-reps", type=int, default=1, help="runs of each C4 / C5 job; the fastest is reported")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: the headline's own steps and nothing else
+        args.no_bsw = args.no_cpu_baseline = args.no_e2e = args.no_c4 = True
 
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
         launch_ranks(args.gpus, args.dry_run)  # exits
@@ -1191,6 +1232,8 @@ def main():
 
     progress("C2 PairHMM")
     ph = bench_phmm(args, dev, rk)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {"phmm_log10_likelihood": ph["out"]})
     total_cells = ph["cells"] * world * args.steps
     value = total_cells / ph["elapsed"] / 1e9
     fwd_s = ph["fwd_ms"] * 1e-3
@@ -1445,9 +1488,11 @@ def dry_main(args, rk):
     rk.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        dry_step(args)
+        last = dry_step(args)
     rk.barrier()
     elapsed, = rk.max(time.perf_counter() - t0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rk.rank, {"dry_step": np.array([last], np.float64)})
     units, = rk.sum(float(args.steps))
     ranks_seen, = rk.sum(1.0)
     rk.cpu_barrier()  # the gloo wait group of the C4 / C5 legs

@@ -568,3 +568,29 @@ def test_column_kernel_class_edges(gpu, tmp_path, k):
     assert "DONE" in r.stdout, r.stderr[-3000:]
     used = check_parity(p, np.load(out), False)
     assert used.sum() > 0, "the fp64 rescue must run on some streamed pairs"
+
+
+def test_bench_plain_run_dumps_the_timed_outputs(gpu, tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` run: N timed steps, a
+    line with the headline fields and ms_per_step and none of the --full legs,
+    and with --dump-outputs the last step's log10 likelihoods of the seeded
+    batch, within the parity bar of the oracle on the same pairs."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--pairs", "3001", "--seed", "77", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=120, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["unit"] == "GCUPS" and line["value"] > 0
+    assert line["higher_is_better"] is True and line["dtype"] == "fp32 (fp64 rescue)"
+    assert not {"bsw", "cpu_baseline", "parity", "e2e", "c4", "c5"} & set(line)
+    assert os.listdir(tmp_path / "out") == ["phmm_log10_likelihood.npy"]
+    got = np.load(tmp_path / "out" / "phmm_log10_likelihood.npy")
+    p = fcship.synth_phmm(77, 3001, R=101, hmin=150, hmax=300)
+    assert got.dtype == np.float64 and got.shape == (p.n_pairs,)
+    ref, _ = oracle_lib.phmm_batch(p)
+    np.testing.assert_allclose(got, ref, rtol=RTOL)

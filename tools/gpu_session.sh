@@ -24,10 +24,10 @@ for step in "$@"; do
     info) run info 60 bash -c 'nproc; free -g; df -h /tmp /dev/shm "$0"; rocm-smi --showuse --showmemuse | head -20' "$ROOT" ;;
     tests) run pytest_gpu 600 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider --timeout 120 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 900 python bench.py ;;
-    benchq) run benchq 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-e2e ;;
+    bench) run bench 900 python bench.py --full ;;
+    benchq) run benchq 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-e2e ;;
     prof) run prof 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-            python3 "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-e2e ;;
+            python3 "$ROOT/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-e2e ;;
     pmc) run pmc 900 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o run --output-format csv -- \
             python3 "$ROOT/bench.py" --steps 1 --warmup 0 --no-cpu-baseline --no-bsw --no-e2e &&
          run pmc2 900 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write" -o run --output-format csv -- \
