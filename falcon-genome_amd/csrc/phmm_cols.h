@@ -30,12 +30,19 @@
 // fill or drain inside a stream, only at its end (15 steps per stream).
 // Per cell the arithmetic is phmm3's exactly (same operations, same order),
 // so the results are bitwise those of the row-streamed kernel.
+// phmm5_kernel (below) is the same kernel with one pair stream per register
+// instead of two packed half-streams; it is the one every class launches, and
+// phmm4_kernel is kept as its bitwise reference (FCSHIP_COLS=packed).
 #pragma once
 
 namespace fcs {
 
 constexpr int kColsClasses = 8;
-constexpr int kColsMinR = 33;  // the next pair's haplotype codes are converted >= 16 rows after a switch
+// The next pair's haplotype codes are converted at the first block start >= 16
+// rows after a switch: <= 23 rows after it with phmm4's 8-step blocks, <= 31
+// with phmm5's 16-step blocks, and the next pair starts R + 2 rows after it, so
+// R >= 29 would do for both; 33 is the streamed kernels' common minimum.
+constexpr int kColsMinR = 33;
 // Columns per lane of launch class c (longest haplotypes first): H <= 16 C - 1.
 __host__ __device__ constexpr int cols_C(int c) { return c == 0 ? 19 : 18 - c; }  // 19, 17, 16, .., 11
 __host__ __device__ constexpr int cols_hmax(int c) { return 16 * cols_C(c) - 1; }
@@ -539,6 +546,366 @@ __global__ __launch_bounds__(64, 2) void phmm4_kernel(
               out[p] = (double)(log10f(acc) - tab.log10_init);
             }
           }
+      }
+    }
+  }
+}
+
+// ---- phmm5: the same kernel with ONE pair stream per register.
+// phmm4 is pinned at 2 waves per SIMD by its registers (195 .. 249 VGPRs) and
+// a packed f32 op issues in the time of its two scalar halves, so packing buys
+// no issue rate and costs the occupancy.  Here a segment carries one stream:
+// the per-lane state is 2 C floats, every v_pk_* is the scalar op on the same
+// operands in the same order (bitwise the same results), all 16 lanes of the
+// segment table hold pairs (K <= 16), and a block is 16 steps (one ring item
+// per lane and block) run as two passes over the 8-step unrolled body.
+// LDS per wave: a 48-row ring per segment (rows t0 - 15 .. t0 + 31 live at
+// once) of five 8-byte chunks per row: {e1, e3}, {my, yy}, {mm, gm}, {mx, xx},
+// {Tlo, Thi} with the Z flag in Thi's byte 3 (no column code selects it: codes
+// end at 6); chunk-major, then segment, then slot, so a segment's 16 lanes
+// read 128 contiguous bytes (up to the wrap).  7,680 B ring + 256 B capture +
+// 1,536 B tables = 9,472 B: 16 waves fit the CU's 160 KB.
+constexpr int kCols1Ring = 48;
+constexpr int kCols1Chunks = 5;
+constexpr int kCols1ChunkBytes = kCols1Ring * 4 * 8;
+constexpr int kCols1CapOff = kCols1Chunks * kCols1ChunkBytes;  // lane 15's D per step of a block (4 x 16 floats)
+constexpr int kCols1TabOff = kCols1CapOff + 4 * 16 * 4;
+constexpr int kCols1Lds = kCols1TabOff + 3 * 128 * 4;
+constexpr int kCols1MaxK = 16;  // pairs per stream: one per lane of the segment table
+// Waves per SIMD the kernel is compiled for: what its registers allow without
+// scratch (tools/kernel_resources.py: 134 VGPRs at C = 11 .. 168 at C = 19, so
+// every class takes 3; 4 waves need <= 128 and spilled 16 .. 84 bytes per lane).
+__host__ __device__ constexpr int cols1_waves(int C) { return 3; }
+static_assert(kCols1Lds <= 10240, "16 waves per CU");
+
+typedef uint32_t pu2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ void cols1_put(unsigned char* smem, int slot, int seg, const ColsItem& c) {
+  unsigned char* const p = smem + (seg * kCols1Ring + slot) * 8;
+  *reinterpret_cast<pf2*>(p) = pf2{c.e1, c.e3};
+  *reinterpret_cast<pf2*>(p + kCols1ChunkBytes) = pf2{c.my, c.yy};
+  *reinterpret_cast<pf2*>(p + 2 * kCols1ChunkBytes) = pf2{c.mm, c.gm};
+  *reinterpret_cast<pf2*>(p + 3 * kCols1ChunkBytes) = pf2{c.mx, c.xx};
+  *reinterpret_cast<pu2*>(p + 4 * kCols1ChunkBytes) = pu2{c.tlo, c.thi | (c.z != 0.f ? 0x01000000u : 0u)};
+}
+
+template <int C>
+__global__ __launch_bounds__(64, cols1_waves(C)) void phmm5_kernel(
+    const PhmmDevBatch b, const int32_t* __restrict__ order, const int64_t* __restrict__ bounds, const int cls,
+    const int K, const int tail_pairs, const PhmmTables<float> gtab, double* __restrict__ out,
+    int32_t* __restrict__ rescue_list, unsigned long long* __restrict__ rescue_count, const float thr,
+    const int use_rescue, int32_t* __restrict__ fb_list, unsigned long long* __restrict__ fb_count) {
+  constexpr int NW = (C + 3) / 4;  // code dwords
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const int lane = threadIdx.x;
+  const int seg = lane >> 4;
+  const int sl = lane & 15;  // lane of the segment, and its entry of the segment table: pair sl of the stream
+  const int sbase = lane & 48;
+  const int i0 = sl * C;  // first haplotype index of this lane's columns
+  const int64_t cbeg = bounds[cls];
+  const long long count = bounds[cls + 1] - cbeg;
+  order += cbeg;
+  PhmmTables<float> tab = gtab;
+  {
+    float* const t = reinterpret_cast<float*>(smem_raw + kCols1TabOff);
+    for (int i = lane; i < 128; i += 64) {
+      t[i] = gtab.ph2pr[i];
+      t[128 + i] = gtab.dmatch[i];
+      t[256 + i] = gtab.dmis[i];
+    }
+    tab.ph2pr = t;
+    tab.dmatch = t + 128;
+    tab.dmis = t + 256;
+  }
+  // Batches: 4 streams per wave, K pairs each, except the range's last
+  // tail_pairs (shortest haplotypes), one pair per stream.
+  const long long tailn = count < (long long)tail_pairs ? count : (long long)tail_pairs;
+  const long long headn = count - tailn;
+  const long long per = 4LL * K;
+  const long long nb_head = (headn + per - 1) / per;
+  const long long nbatch = nb_head + (tailn + 3) / 4;
+
+  for (long long w = blockIdx.x; w < nbatch; w += gridDim.x) {
+    const bool head = w < nb_head;
+    const int Kb = head ? K : 1;
+    const long long bstart = head ? w * per : headn + (w - nb_head) * 4;
+    const long long bend = head ? min(headn, bstart + per) : min(count, bstart + 4);
+    // Segment table: lane sl holds pair sl of the segment's stream (stream seg
+    // of the batch takes every 4th pair).
+    const long long idx = bstart + seg + 4LL * sl;
+    const int pm = (sl < Kb && idx < bend) ? order[idx] : -1;
+    int Rm = 0, Hm = 0;
+    int64_t rom = 0, hom = 0;
+    float Im = 0.f;
+    if (pm >= 0) {
+      const int ri = b.pair_read[pm], hi = b.pair_hap[pm];
+      Rm = b.read_len[ri];
+      Hm = b.hap_len[hi];
+      rom = b.read_off[ri];
+      hom = b.hap_off[hi];
+      Im = tab.init_const / (float)Hm;
+    }
+    const int len = pm >= 0 ? Rm + 2 : 0;  // rows 1..R, V, Z
+    int incl = len;
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1) {
+      const int v = __shfl_up(incl, d, 16);
+      if (sl >= d) incl += v;
+    }
+    const int Gm = incl - len;  // first stream row of the pair
+    const int tot = __builtin_amdgcn_ds_bpermute(4 * (sbase + 15), incl);
+    const int nsteps = ((wave_max(tot) + 15) + 15) & ~15;
+    int sb = sbase * 4;  // laundered once per block, as in phmm4
+    auto bp = [&](int v, int k) { return __builtin_amdgcn_ds_bpermute(sb + 4 * min(k, 15), v); };
+    auto tG = [&](int k) { return bp(Gm, k); };
+    auto tR = [&](int k) { return bp(Rm, k); };
+    auto tH = [&](int k) { return bp(Hm, k); };
+    auto tP = [&](int k) { return bp(pm, k); };
+    auto tI = [&](int k) { return __int_as_float(bp(__float_as_int(Im), k)); };
+    auto t64 = [&](int64_t v, int k) {
+      const int lo = bp((int)v, k), hi = bp((int)(v >> 32), k);
+      return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
+    };
+    auto valid = [&](int k) {  // the shuffle runs in every lane whatever k is
+      const int pv = tP(k);
+      return k < Kb && pv >= 0;
+    };
+
+    // Haplotype codes: cur (in use), nxt (the stream's next pair, taken by
+    // lane l at stream row swr, i.e. step swr + l), nk = the pair held in nxt.
+    // other: bit k = pair k has a haplotype byte outside A/C/G/T/N.
+    uint32_t cur[NW], nxt[NW];
+    int nk, swr;
+    unsigned other = 0u;
+    auto fetch_codes = [&](int k, uint32_t (&dst)[NW]) {  // uniform: every lane of the wave calls it
+      const bool ok = valid(k);
+      const int Hk = tH(k);
+      const int H = ok ? Hk : 0;
+      const int64_t ho = t64(hom, k);
+      uint32_t raw[NW + 1];
+      int al;
+      cols_load<NW>(b.hb, ok ? ho : 0, H, i0, raw, al);
+      bool oth = false;
+      cols_convert<NW>(raw, al, i0, H, dst, oth);
+      const unsigned long long bal = __ballot(oth && ok);
+      if (((bal >> sbase) & 0xFFFFull) != 0ull) other |= 1u << k;
+    };
+#pragma unroll
+    for (int d = 0; d < NW; ++d) cur[d] = 0x06060606u;
+    fetch_codes(0, nxt);
+    nk = 0;
+    swr = valid(0) ? tG(0) : 0x3FFFFFFF;
+    // Capture: lane 15 takes the sum at the V row of pair kc.
+    int kc = 0, cap, capp;
+    auto load_cap = [&] {
+      const bool ok = valid(kc);
+      const int v = tG(kc) + tR(kc);
+      cap = ok ? v : -0x3FFFFFFF;  // stream row of the V row
+      capp = tP(kc);
+    };
+    load_cap();
+
+    // The ring's items (row base + sl per lane) in two stages one block apart.
+    int kp = 0;  // stage A's cursor: the pair holding this lane's item row
+    RawRow praw{-1, 0, 0, 0, 0, 0, 0};
+    int prole = 0;  // role | first << 4
+    float pih = 0.f;
+    bool kok = false, nok = false;
+    int kG = 0, kR = 0, nG = 0;
+    float kI = 0.f;
+    int64_t kro = 0;
+    auto load_cursor = [&] {
+      kok = valid(kp);
+      kG = tG(kp);
+      kR = tR(kp);
+      kI = tI(kp);
+      kro = t64(rom, kp);
+      nok = valid(kp + 1);
+      nG = tG(kp + 1);
+    };
+    load_cursor();
+    auto stage_a = [&](int base) {
+      const int g = base + sl;
+      const bool adv = nok && g >= nG;  // pairs span >= 35 rows: at most one advance per 16 rows
+      if (__ballot(adv) != 0ull) {
+        if (adv) ++kp;
+        load_cursor();
+      }
+      const int r = g - kG;
+      int role = 0;
+      if (kok && r >= 0 && r < kR) role = r == kR - 1 ? 3 : 2;
+      else if (kok && r == kR) role = 4;
+      pih = kI;
+      prole = role | (r == 0 ? 16 : 0);
+      praw = (role == 2 || role == 3) ? load_raw(b, kR, kro, r) : RawRow{-1, 0, 0, 0, 0, 0, 0};
+    };
+    auto stage_b = [&](int base) {  // base >= 0
+      cols1_put(smem_raw, (int)((unsigned)(base + sl) % (unsigned)kCols1Ring), seg,
+                cols_item(tab, praw, prole & 15, (prole & 16) != 0, pih));
+    };
+    {  // ring prologue: rows -16..-1 are Z (slots 32..47), rows 0..15 built, rows 16..31 requested
+      cols1_put(smem_raw, 32 + sl, seg, cols_item(tab, RawRow{-1, 0, 0, 0, 0, 0, 0}, 0, false, 0.f));
+      stage_a(0);
+      stage_b(0);
+      stage_a(16);
+    }
+
+    float Xn[C], In[C];
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+      Xn[j] = 1.f;
+      In[j] = 0.f;
+    }
+    float dn = 1.f, xo = 1.f, xin = 1.f;
+    const uint32_t segoff = (uint32_t)seg * (kCols1Ring * 8u) + lds_addr(smem_raw);
+
+    for (int t0 = 0; t0 < nsteps; t0 += 16) {
+      asm volatile("" : "+v"(sb));
+      // Next pair's codes: once every lane took the pair in nxt (lane 15 reached
+      // row swr before this block), convert the one after it.  The block starts
+      // at most 31 rows after swr and the next pair at swr + R + 2 >= swr + 35.
+      {
+        const bool ev = swr + 16 <= t0 && nk + 1 < Kb;
+        if (__ballot(ev) != 0ull) {  // uniform: fetch_codes shuffles
+          uint32_t tmp[NW];
+          fetch_codes(nk + 1, tmp);
+          const bool vn = valid(nk + 1);
+          const int gn = tG(nk + 1);
+          if (ev) {
+#pragma unroll
+            for (int d = 0; d < NW; ++d) nxt[d] = tmp[d];
+            ++nk;
+            swr = vn ? gn : 0x3FFFFFFF;
+          }
+        }
+        if (swr + 16 <= t0 && nk + 1 >= Kb) swr = 0x3FFFFFFF;  // last pair taken
+      }
+      // The ring's rows t0 + 16 .. t0 + 31 (slots of rows t0 - 32 .. t0 - 17,
+      // read last in the previous block), requested one block ago; then the
+      // requests for rows t0 + 32 .. t0 + 47.
+      stage_b(t0 + 16);
+      stage_a(t0 + 32);
+      {
+        const bool adv = cap >= 0 && cap + 15 < t0;  // lane 15 passed the V row in an earlier block
+        if (__ballot(adv) != 0ull) {
+          if (adv) ++kc;
+          load_cap();
+        }
+      }
+      const bool capo = (other >> kc) & 1u;
+      const int gb = t0 - sl;  // this lane's row at the block's first step
+      const bool any_cap = __ballot(sl == 15 && (unsigned)(cap - gb) < 16u) != 0ull;
+      // steps of this block at which some lane takes its next haplotype codes
+      // (lane l of segment q switches at step swr - t0 + l): a uniform 16-bit mask
+      unsigned swmask = 0u;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int lo = __builtin_amdgcn_readlane(swr, 16 * q) - t0;  // steps lo .. lo + 15
+        if (lo < 16 && lo + 15 >= 0) {
+          const int a = max(lo, 0), bnd = min(lo + 15, 15);
+          swmask |= ((2u << bnd) - 1u) & ~((1u << a) - 1u);
+        }
+      }
+      uint32_t xs = ((uint32_t)(gb + kCols1Ring) % (uint32_t)kCols1Ring) * 8u;  // gb >= -15
+      uint32_t capa = lds_addr(smem_raw) + kCols1CapOff + seg * 64;
+      int g0 = gb;
+
+#pragma nounroll
+      for (int pass = 0; pass < 2; ++pass) {
+        auto step = [&](auto S_) {
+          constexpr int S = decltype(S_)::value;
+          const int g = g0 + S;
+          if (swmask & (1u << S)) {  // uniform
+            const bool take = g == swr;
+#pragma unroll
+            for (int d = 0; d < NW; ++d) {
+              uint32_t r;
+              asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(cur[d]), "v"(nxt[d]), "s"(__ballot(take)));
+              cur[d] = r;
+            }
+          }
+          asm volatile("" ::: "memory");
+          const uint32_t a0 = xs + (uint32_t)(S * 8);  // < 2 * 48 * 8: one subtraction wraps
+          const uint32_t pa = min(a0, a0 - (uint32_t)(kCols1Ring * 8)) + segoff;
+          auto ld2 = [&](int chunk) {
+            return *reinterpret_cast<const __attribute__((address_space(3))) pf2*>((uintptr_t)(pa + chunk * kCols1ChunkBytes));
+          };
+          const pf2 r0 = ld2(0), r1 = ld2(1), r2 = ld2(2), r3 = ld2(3);
+          const pu2 cr = *reinterpret_cast<const __attribute__((address_space(3))) pu2*>((uintptr_t)(pa + 4 * kCols1ChunkBytes));
+          const float e1 = r0.x, e3 = r0.y, my = r1.x, yy = r1.y, mm = r2.x, gm = r2.y, mx = r3.x, xx = r3.y;
+          const float z = (float)(cr.y >> 24);  // v_cvt_f32_ubyte3: 1 on Z rows
+          // the lane below's D into column l*C + 1 (lane 0: 1 on Z rows, else
+          // 0) and its X(g, l*C) for the next row (lane 0: X(g, 0) = 1 after a Z row)
+          const float din = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(z), __float_as_int(dn), kDppRowShr1, 0xF, 0xF, false));
+          const float xnx = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(z), __float_as_int(xo), kDppRowShr1, 0xF, 0xF, false));
+          const float xcur = xin;
+          xin = xnx;
+          uint32_t mA = 0;
+          auto prior = [&](int j, const float dep) {  // tied to the previous column's D, as in phmm4
+            if ((j & 3) == 0) mA = __builtin_amdgcn_perm(cr.y, cr.x, cur[j >> 2]);
+            int a;
+            asm volatile("v_bfe_i32 %0, %1, %2, 1" : "=v"(a) : "v"(mA), "i"(8 * (j & 3)), "v"(dep));
+            return sel_v((uint32_t)a, e1, e3);
+          };
+          float Mn = xcur * prior(0, xcur);
+          float D = din, Mp = 0.f, Dp = 0.f;
+#pragma unroll
+          for (int j = 0; j < C; ++j) {
+            const float M = Mn;
+            if (j > 0) D = __builtin_fmaf(Mp, my, Dp * yy);
+            float I = In[j], Xo = Xn[j];
+            asm volatile("" : "+v"(I), "+v"(Xo) : "v"(D));
+            if (j + 1 < C) Mn = Xo * prior(j + 1, D);
+            float xn = __builtin_fmaf(M, mm, __builtin_fmaf(I, gm, D));
+            float in = __builtin_fmaf(M, mx, I * xx);
+            asm volatile("" : "+v"(xn), "+v"(in));
+            Xn[j] = xn;
+            In[j] = in;
+            Mp = M;
+            Dp = D;
+          }
+          dn = __builtin_fmaf(Mp, my, Dp * yy);
+          xo = Xn[C - 1];
+          // lane 15's D entering column 16 C + 1, kept per step in LDS: at a V
+          // row it is the stream's sum, taken after the block
+          uint64_t keep;
+          const uint32_t cpa = capa + 0u;
+          const float dnv = dn;
+          asm volatile(
+              "s_mov_b64 %0, exec\n\t"
+              "s_mov_b64 exec, %3\n\t"
+              "ds_write_b32 %1, %2 offset:%4\n\t"
+              "s_mov_b64 exec, %0"
+              : "=&s"(keep)
+              : "v"(cpa), "v"(dnv), "s"(kTopLanes), "i"(4 * S)
+              : "memory");
+        };
+        [&]<int... S>(std::integer_sequence<int, S...>) {
+          (step(std::integral_constant<int, S>{}), ...);
+        }(std::make_integer_sequence<int, 8>{});
+        g0 += 8;
+        swmask >>= 8;
+        capa += 32;
+        xs += 64;
+        xs = min(xs, xs - (uint32_t)(kCols1Ring * 8));
+      }
+      if (any_cap) {
+        // lane 15 at a V row: the D entering column 16 C + 1 is the stream's sum
+        if (sl == 15 && (unsigned)(cap - gb) < 16u) {
+          const float acc = *reinterpret_cast<const float*>(smem_raw + kCols1CapOff + seg * 64 + 4 * (cap - gb));
+          const int p = capp;
+          if (capo) {
+            const unsigned long long k = atomicAdd(fb_count, 1ull);
+            fb_list[k] = p;
+            out[p] = __builtin_nan("");
+          } else if (use_rescue && acc < thr) {
+            const unsigned long long k = atomicAdd(rescue_count, 1ull);
+            rescue_list[k] = p;
+            out[p] = __builtin_nan("");
+          } else {
+            out[p] = (double)(log10f(acc) - tab.log10_init);
+          }
+        }
       }
     }
   }

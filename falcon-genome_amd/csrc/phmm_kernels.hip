@@ -33,6 +33,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 
 #include <utility>
 
@@ -642,6 +643,40 @@ static int cols_pairs_per_half(int64_t n) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(8, k));
 }
 
+// Pairs per stream of the single-stream column kernel (phmm5): as many as keep
+// >= ~32K waves for the batch (4 streams per wave; about ten rounds of the
+// chip's 1024 SIMDs x 3 wave slots; 7 on 1M pairs, where 5 and 10 measured
+// slower), at most one per lane of the segment table.  FCSHIP_STREAM_K=k
+// (tests) forces k here too, and then shrinks the one-pair-per-stream tail to
+// a single batch so that test-sized classes run k-pair streams at all.
+static int cols1_forced_k() {
+  static const int forced = [] {
+    const char* e = std::getenv("FCSHIP_STREAM_K");
+    return e ? std::atoi(e) : 0;
+  }();
+  return forced > 0 ? std::min(forced, kCols1MaxK) : 0;
+}
+static int cols1_pairs_per_stream(int64_t n) {
+  if (const int f = cols1_forced_k()) return f;
+  const int64_t k = n / (4 * 32768);
+  return (int)std::max<int64_t>(1, std::min<int64_t>(kCols1MaxK, k));
+}
+
+// Which column kernel a class launches: the single-stream phmm5 where it
+// measured faster than phmm4 (every class; the long classes
+// were checked with a mixed dispatch, which lost 3.5%), phmm4 otherwise.
+// FCSHIP_COLS=packed|single (tests, A/B) forces one kernel for every class.
+static bool cols_single(int c) {
+  static const int forced = [] {
+    const char* e = std::getenv("FCSHIP_COLS");
+    if (!e) return 0;
+    return !std::strcmp(e, "single") ? 1 : !std::strcmp(e, "packed") ? 2 : 0;
+  }();
+  if (forced) return forced == 1;
+  static constexpr bool kSingle[kColsClasses] = {true, true, true, true, true, true, true, true};
+  return kSingle[c];
+}
+
 int launch_phmm_forward(const PhmmDevBatch& b, const int32_t* order, int64_t count, int max_hap_len,
                         const int64_t* bounds, const DeviceTables& t, bool exact, double* out, int32_t* rescue_list,
                         unsigned long long* rescue_count, float thr, bool use_rescue, int32_t* fb_list,
@@ -702,6 +737,34 @@ int launch_phmm_forward(const PhmmDevBatch& b, const int32_t* order, int64_t cou
       const int rc = launch_one<float, true, false>(b, order, nullptr, count, bounds, j,
                                                    nslot_for(std::min(cols_hmax(c), max_hap_len)), groups, t.tf, out,
                                                    rescue_list, rescue_count, thr, use_rescue, st);
+      if (rc != FCS_OK) return rc;
+      continue;
+    }
+    if (cols_single(c)) {
+      const int K = cols1_pairs_per_stream(count);
+      // the range's last pairs run one per stream: about one round of the
+      // chip's wave slots (256 CUs x 4 SIMDs x w waves x 4 streams)
+      const int tail = cols1_forced_k() ? 4 : 1024 * cols1_waves(cols_C(c)) * 4;
+      const unsigned grid = (unsigned)std::min<long long>(
+          std::max<long long>((count + 4 * K - 1) / (4 * K) + (tail + 3) / 4, 1), 65536);
+      auto launch = [&](auto kern) -> int {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64), (size_t)kCols1Lds, st, b, order, bounds, j, K, tail, t.tf, out,
+                           rescue_list, rescue_count, thr, use_rescue ? 1 : 0, fb_list, fb_count);
+        FCS_HIP_CHECK(hipGetLastError());
+        return FCS_OK;
+      };
+      static_assert(cols_C(0) == 19 && cols_C(1) == 17 && cols_C(7) == 11 && kColsClasses == 8, "launch table below");
+      int rc;
+      switch (cols_C(c)) {
+        case 19: rc = launch(phmm5_kernel<19>); break;
+        case 17: rc = launch(phmm5_kernel<17>); break;
+        case 16: rc = launch(phmm5_kernel<16>); break;
+        case 15: rc = launch(phmm5_kernel<15>); break;
+        case 14: rc = launch(phmm5_kernel<14>); break;
+        case 13: rc = launch(phmm5_kernel<13>); break;
+        case 12: rc = launch(phmm5_kernel<12>); break;
+        default: rc = launch(phmm5_kernel<11>); break;
+      }
       if (rc != FCS_OK) return rc;
       continue;
     }
