@@ -492,14 +492,16 @@ struct fcs_phmm_plan {
   int32_t* idx_out = nullptr;  // the schedule: pair indices, launch class by class
   int32_t* rescue_list = nullptr;
   int32_t* fb_list = nullptr;                  // pairs the streamed kernel hands back (bytes outside ACGTN)
-  unsigned long long* rescue_count = nullptr;  // [0] rescue count, [1] fallback count, then int64 class bounds
+  // [0] rescue count, [1] fallback count, [2 ..] the column classes' queue heads (kPhmmCounters words, zeroed
+  // together), then the int64 class bounds
+  unsigned long long* rescue_count = nullptr;
   unsigned long long* fb_count = nullptr;
   int64_t* bounds = nullptr;
   uint32_t* bin_hist = nullptr;    // the bin schedule's histogram (kept zero between schedules)
   uint32_t* bin_cursor = nullptr;  // and its running bin starts
   bool bin_zeroed = false;         // bin_hist zeroed on a schedule stream (then kept zero by the scan)
   int64_t scheduled = -1;  // n_pairs of the last schedule
-  bool counters_zeroed = false;  // the last schedule's count kernel zeroed rescue_count[0..1]
+  bool counters_zeroed = false;  // the last schedule's count kernel zeroed rescue_count[0 .. kPhmmCounters - 1]
 };
 
 namespace fcs {
@@ -652,14 +654,14 @@ int fcs_phmm_plan_create(int32_t device, int64_t max_pairs, fcs_phmm_plan** plan
   FCS_HIP_CHECK(hipMalloc(&p->idx_out, n * 4));
   FCS_HIP_CHECK(hipMalloc(&p->rescue_list, n * 4));
   FCS_HIP_CHECK(hipMalloc(&p->fb_list, n * 4));
-  FCS_HIP_CHECK(hipMalloc(&p->rescue_count, (2 + kPhmmLaunchClasses + 1) * sizeof(unsigned long long)));
+  FCS_HIP_CHECK(hipMalloc(&p->rescue_count, (kPhmmCounters + kPhmmLaunchClasses + 1) * sizeof(unsigned long long)));
   // Nothing is initialised here: every run writes the class bounds (the bounds
   // kernel stores all kPhmmClasses + 1 of them) and zeroes the rescue count on
   // the caller's stream.  (Round 1 zeroed them with a null-stream hipMemset,
   // which does not order against the non-blocking streams the plan runs on and
   // once landed after a schedule, so class launches computed nothing.)
   p->fb_count = p->rescue_count + 1;
-  p->bounds = reinterpret_cast<int64_t*>(p->rescue_count + 2);
+  p->bounds = reinterpret_cast<int64_t*>(p->rescue_count + kPhmmCounters);
   constexpr size_t kBins = (size_t)1 << (kPhmmKeyBits - 4);
   FCS_HIP_CHECK(hipMalloc(&p->bin_hist, 2 * kBins * sizeof(uint32_t)));
   p->bin_cursor = p->bin_hist + kBins;
@@ -724,14 +726,15 @@ int fcs_phmm_dev_forward(fcs_phmm_plan* plan, const fcs_phmm_batch* b, double* o
   rc = get_device_tables(plan->device, &t);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  // rescue + fallback counts: zeroed by the schedule's keys kernel for the first
-  // forward pass after it, by a memset for any further pass
+  // rescue + fallback counts and the queue heads: zeroed by the schedule's count
+  // kernel for the first forward pass after it, by a memset for any further pass
   if (!plan->counters_zeroed)
-    FCS_HIP_CHECK(hipMemsetAsync(plan->rescue_count, 0, 2 * sizeof(unsigned long long), s));
+    FCS_HIP_CHECK(hipMemsetAsync(plan->rescue_count, 0, kPhmmCounters * sizeof(unsigned long long), s));
   plan->counters_zeroed = false;
   return launch_phmm_forward(to_dev(b), plan->idx_out, b->n_pairs, std::max(b->max_hap_len, 1), plan->bounds, *t,
                              opts->exact_order != 0, out, plan->rescue_list, plan->rescue_count,
-                             opts->rescue_threshold, opts->use_fp64_rescue != 0, plan->fb_list, plan->fb_count, s);
+                             opts->rescue_threshold, opts->use_fp64_rescue != 0, plan->fb_list, plan->fb_count,
+                             plan->rescue_count + kPhmmQueueHead0, s);
 }
 
 int fcs_phmm_dev_rescue(fcs_phmm_plan* plan, const fcs_phmm_batch* b, double* out, const fcs_phmm_opts* opts,

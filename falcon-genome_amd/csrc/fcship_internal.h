@@ -163,17 +163,20 @@ int join_streams(hipStream_t s, const hipStream_t (&fs)[kForkStreams]);
 // ------------------------------------------------------------ kernel launchers
 // The bin schedule (counting sort on the key's top 12 bits): idx_out = the
 // pairs in bin order, bounds = device int64[kPhmmLaunchClasses + 1] (the first
-// position of each launch class, then n), counters[0..1] (the forward pass's
-// rescue and fallback counts) zeroed; hist / cursor are
+// position of each launch class, then n), counters[0 .. kPhmmCounters - 1] (the
+// forward pass's rescue and fallback counts, then the column classes' queue
+// heads) zeroed; hist / cursor are
 // uint32[1 << (kPhmmKeyBits - 4)], hist all zero on entry (left zero).
 int launch_phmm_bin_schedule(const PhmmDevBatch& b, int32_t* idx_out, int64_t* bounds, unsigned long long* counters,
                              uint32_t* hist, uint32_t* cursor, hipStream_t s);
 // fb_list / fb_count: pairs the streamed kernel hands back (haplotype bytes
 // outside A/C/G/T/N), recomputed by the one-row kernel within this call.
+// qheads: kColsLaunch queue head words (phmm6_kernel: the next position of the class to hand out, one word
+// per column class), zero on entry.
 int launch_phmm_forward(const PhmmDevBatch& b, const int32_t* order, int64_t count, int max_hap_len,
                         const int64_t* bounds, const DeviceTables& t, bool exact, double* out, int32_t* rescue_list,
                         unsigned long long* rescue_count, float thr, bool use_rescue, int32_t* fb_list,
-                        unsigned long long* fb_count, hipStream_t s);
+                        unsigned long long* fb_count, unsigned long long* qheads, hipStream_t s);
 int launch_phmm_rescue(const PhmmDevBatch& b, const int32_t* list, const unsigned long long* count_dev,
                        int64_t max_count, int max_hap_len, const DeviceTables& t, bool exact, double* out,
                        hipStream_t s);
@@ -237,6 +240,10 @@ constexpr int kPhmmClasses = 6;
 constexpr int kLongClasses = 2;  // phmm3 stream classes 3 and 2 (H <= 3700, <= 472)
 constexpr int kColsLaunch = 8;   // phmm_cols.h classes (H <= 303, <= 271, .., <= 175)
 constexpr int kPhmmLaunchClasses = kLongClasses + kColsLaunch + kPhmmClasses;
+// The plan's counter words, zeroed together before every forward pass: [0] the
+// rescue count, [1] the fallback count, [2 ..] one queue head per column class.
+constexpr int kPhmmQueueHead0 = 2;
+constexpr int kPhmmCounters = kPhmmQueueHead0 + kColsLaunch;
 // Sorted schedule: one launch over the lane (0..9) and pair (kBswPairBucket0..+4)
 // buckets, then the wave-per-task kernel over kBswWideBucket.
 int launch_bsw_extend_sorted(const BswDevBatch& b, const BswParams& p, int max_qlen, int max_tlen, int32_t* res,

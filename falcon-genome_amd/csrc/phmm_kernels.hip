@@ -493,10 +493,7 @@ __global__ __launch_bounds__(kBinBlock) void phmm_bin_count_kernel(const PhmmDev
                                                                     unsigned long long* __restrict__ counters) {
   __shared__ uint32_t h[kPhmmBins];
   for (int i = threadIdx.x; i < kPhmmBins; i += kBinBlock) h[i] = 0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    counters[0] = 0ull;
-    counters[1] = 0ull;
-  }
+  if (blockIdx.x == 0 && threadIdx.x < kPhmmCounters) counters[threadIdx.x] = 0ull;
   __syncthreads();
   const long long base = (long long)blockIdx.x * (kBinBlock * kBinItems);
   for (int k = 0; k < kBinItems; ++k) {
@@ -665,22 +662,50 @@ static int cols1_pairs_per_stream(int64_t n) {
 // Which column kernel a class launches: the single-stream phmm5 where it
 // measured faster than phmm4 (every class; the long classes
 // were checked with a mixed dispatch, which lost 3.5%), phmm4 otherwise.
-// FCSHIP_COLS=packed|single (tests, A/B) forces one kernel for every class.
-static bool cols_single(int c) {
+// The queue-fed phmm6 (continuous streams on a persistent grid) where that
+// measured faster again.
+// FCSHIP_COLS=queue|single|packed (tests, A/B) forces phmm6 / phmm5 / phmm4
+// for every class.
+enum ColsKernel { kColsPacked = 0, kColsSingle = 1, kColsQueue = 2 };
+static ColsKernel cols_kernel(int c) {
   static const int forced = [] {
     const char* e = std::getenv("FCSHIP_COLS");
-    if (!e) return 0;
-    return !std::strcmp(e, "single") ? 1 : !std::strcmp(e, "packed") ? 2 : 0;
+    if (!e) return -1;
+    return !std::strcmp(e, "queue")    ? (int)kColsQueue
+           : !std::strcmp(e, "single") ? (int)kColsSingle
+           : !std::strcmp(e, "packed") ? (int)kColsPacked
+                                       : -1;
   }();
-  if (forced) return forced == 1;
-  static constexpr bool kSingle[kColsClasses] = {true, true, true, true, true, true, true, true};
-  return kSingle[c];
+  if (forced >= 0) return (ColsKernel)forced;
+  static constexpr ColsKernel kDefault[kColsClasses] = {kColsQueue, kColsQueue, kColsQueue, kColsQueue,
+                                                        kColsQueue, kColsQueue, kColsQueue, kColsQueue};
+  return kDefault[c];
+}
+
+// FCSHIP_QUEUE_WAVES=n (tests) caps the workgroups of a phmm6 class launch, so
+// that a test-sized class runs streams tens of pairs long and reuses the
+// slots of the segment table.  phmm6 does not read FCSHIP_STREAM_K.
+static int cols6_forced_waves() {
+  static const int forced = [] {
+    const char* e = std::getenv("FCSHIP_QUEUE_WAVES");
+    return e ? std::atoi(e) : 0;
+  }();
+  return forced > 0 ? forced : 0;
+}
+// One round of the chip: CUs x 4 SIMDs x kCols6Waves workgroups of one wave.
+static int cols6_grid() {
+  if (const int f = cols6_forced_waves()) return f;
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+    cus = 256;
+  return cus * 4 * kCols6Waves;
 }
 
 int launch_phmm_forward(const PhmmDevBatch& b, const int32_t* order, int64_t count, int max_hap_len,
                         const int64_t* bounds, const DeviceTables& t, bool exact, double* out, int32_t* rescue_list,
                         unsigned long long* rescue_count, float thr, bool use_rescue, int32_t* fb_list,
-                        unsigned long long* fb_count, hipStream_t s) {
+                        unsigned long long* fb_count, unsigned long long* qheads, hipStream_t s) {
   if (count <= 0) return FCS_OK;
   const long long groups = (count + 3) / 4;
   const int ns_max = nslot_for(max_hap_len);
@@ -740,7 +765,33 @@ int launch_phmm_forward(const PhmmDevBatch& b, const int32_t* order, int64_t cou
       if (rc != FCS_OK) return rc;
       continue;
     }
-    if (cols_single(c)) {
+    const ColsKernel ck = cols_kernel(c);
+    if (ck == kColsQueue) {
+      const unsigned grid = (unsigned)cols6_grid();
+      auto launch = [&](auto kern) -> int {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64), (size_t)kCols6Lds, st, b, order, bounds, j, t.tf, out,
+                           rescue_list, rescue_count, thr, use_rescue ? 1 : 0, fb_list, fb_count, qheads + c);
+        FCS_HIP_CHECK(hipGetLastError());
+        return FCS_OK;
+      };
+      static_assert(cols_C(0) == 19 && cols_C(1) == 17 && cols_C(7) == 11 && kColsClasses == 8 &&
+                        kColsLaunch == kColsClasses,
+                    "launch table below, one head word per class");
+      int rc;
+      switch (cols_C(c)) {
+        case 19: rc = launch(phmm6_kernel<19>); break;
+        case 17: rc = launch(phmm6_kernel<17>); break;
+        case 16: rc = launch(phmm6_kernel<16>); break;
+        case 15: rc = launch(phmm6_kernel<15>); break;
+        case 14: rc = launch(phmm6_kernel<14>); break;
+        case 13: rc = launch(phmm6_kernel<13>); break;
+        case 12: rc = launch(phmm6_kernel<12>); break;
+        default: rc = launch(phmm6_kernel<11>); break;
+      }
+      if (rc != FCS_OK) return rc;
+      continue;
+    }
+    if (ck == kColsSingle) {
       const int K = cols1_pairs_per_stream(count);
       // the range's last pairs run one per stream: about one round of the
       // chip's wave slots (256 CUs x 4 SIMDs x w waves x 4 streams)

@@ -14,7 +14,7 @@ cells = float(sys.argv[3]) if len(sys.argv) > 3 else 22721383941.0
 tot = {}
 for f in glob.glob(os.path.join(src, "**", "*counter_collection.csv"), recursive=True):
     for r in csv.DictReader(open(f)):
-        if any(k in r["Kernel_Name"] for k in ("phmm5_kernel", "phmm4_kernel", "phmm3_kernel", "phmm2_kernel",
+        if any(k in r["Kernel_Name"] for k in ("phmm6_kernel", "phmm5_kernel", "phmm4_kernel", "phmm3_kernel", "phmm2_kernel",
                                                "phmm_kernel<float, false, false")):
             tot[r["Counter_Name"]] = tot.get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
 q = {k: v / passes for k, v in sorted(tot.items())}
