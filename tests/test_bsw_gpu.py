@@ -9,32 +9,9 @@ import pytest
 
 import fcship
 import oracle_lib
+from sw_dispatch import align_items, related_pair
 
 pytestmark = pytest.mark.gpu
-
-
-def related_pair(rng, qlen, tlen, sub=0.03, indel=0.01, n_frac=0.0):
-    t = rng.integers(0, 4, tlen).astype(np.uint8)
-    q = []
-    i = 0
-    while len(q) < qlen:
-        u = rng.random()
-        if u < indel / 2:
-            q.append(int(rng.integers(0, 4)))
-            continue
-        if u < indel:
-            i += 1
-            continue
-        b = int(t[i % tlen]) if tlen else int(rng.integers(0, 4))
-        if rng.random() < sub:
-            b = (b + 1 + int(rng.integers(0, 3))) & 3
-        q.append(b)
-        i += 1
-    q = np.array(q[:qlen], np.uint8)
-    if n_frac:
-        q[rng.random(qlen) < n_frac] = 4
-        t[rng.random(tlen) < n_frac] = 4
-    return q, t
 
 
 def random_tasks(seed, n, qmax=260, wmax=120):
@@ -344,34 +321,9 @@ def test_global_dev_direction_layouts(gpu, gap):
         assert np.array_equal(got, rc), f"task {k}: {fcship.cigar_str(got)} != {fcship.cigar_str(rc)}"
 
 
-def align_tasks(seed, n, qmin=20, qmax=200, tmin=40, tmax=700, related=0.7):
-    """Mate-rescue-shaped ksw_align2 tasks: a query that is (mostly) a mutated
-    piece of its target window, sometimes twice (score2), sometimes unrelated."""
-    rng = np.random.default_rng(seed)
-    items = []
-    for k in range(n):
-        ql = int(rng.integers(qmin, qmax + 1))
-        tl = int(rng.integers(tmin, tmax + 1))
-        t = rng.integers(0, 4, tl).astype(np.uint8)
-        if rng.random() < related and tl > 8:
-            a = int(rng.integers(0, max(1, tl - ql // 2)))
-            q, _ = related_pair(rng, ql, ql, sub=0.03, indel=0.01)
-            piece = t[a:a + ql]
-            q = piece.copy() if rng.random() < 0.5 else q
-            if len(q) > 4:
-                for j in range(len(q)):
-                    if rng.random() < 0.04:
-                        q[j] = (q[j] + 1) % 4
-            if rng.random() < 0.3 and tl > 2 * len(q) + 10:  # a second, weaker copy far away
-                b = int(rng.integers(0, tl - len(q)))
-                t[b:b + len(q)] = q
-                t[b + len(q) // 2] = (t[b + len(q) // 2] + 1) % 4
-        else:
-            q = rng.integers(0, 4, ql).astype(np.uint8)
-        if rng.random() < 0.05:
-            q[int(rng.integers(0, len(q)))] = 4  # N
-        items.append((np.asarray(q, np.uint8), t, 0, 0))
-    return fcship.make_tasks(items)
+def align_tasks(seed, n, **kw):
+    """Mate-rescue-shaped ksw_align2 tasks (sw_dispatch.align_items)."""
+    return fcship.make_tasks(align_items(seed, n, **kw))
 
 
 @pytest.mark.parametrize("xbyte", [True, False])

@@ -312,3 +312,141 @@ def test_ksw_align2_sse_equals_emulation():
         a = oracle_lib.ksw_align2(q, t, m, x, od, ed, oi, ei)
         b = oracle_lib.ksw_align2_sse(q, t, m, x, od, ed, oi, ei)
         assert a == b, (k, ql, tl, hex(x), a, b)
+
+
+# ------------------------------------------------------------ the kernel-selection edges' input space
+# tests/test_bsw_dispatch_gpu.py judges the GPU by this oracle on other matrices
+# and gap costs than bwa's defaults; the cross-checks above, on those inputs
+# (sw_dispatch's builders), pin the reference a second time there.
+import sw_dispatch as D  # noqa: E402
+
+
+def _both_align(q, t, mat, x, gaps):
+    a = oracle_lib.ksw_align2(q, t, mat, x, *gaps)
+    b = oracle_lib.ksw_align2_sse(q, t, mat, x, *gaps)
+    assert a == b, (len(q), len(t), hex(x), mat.tolist(), gaps, a, b)
+    return a
+
+
+@pytest.mark.parametrize("name", sorted(D.ALIGN_MATS))
+def test_ksw_align2_sse_equals_emulation_other_matrices(name):
+    """All seven fields, the four xtra runs of each matrix, saturating u8
+    tasks included."""
+    mat = D.ALIGN_MATS[name]
+    items, runs = D.align_matrix_runs(name)
+    sat = 0
+    for run, xs in runs.items():
+        for (q, t, _, _), x in zip(items, xs):
+            sat += _both_align(q, t, mat, int(x), (6, 1, 6, 1))[0] == 255 and bool(x & D.KSW_XBYTE)
+    assert (sat > 0) == (name in ("2_8_2", "3_5_1", "5_16_1", "15_16_3", "asym"))
+
+
+def test_ksw_align2_sse_equals_emulation_selection_edges():
+    """The saturation-edge, wave-split, gap-edge and matrix-support batches."""
+    for name, path, mat, gaps, items, x, want in D.align_saturation_cases():
+        for q, t, _, _ in items:
+            _both_align(q, t, mat, x, gaps)
+            _both_align(q, t, mat, x & ~D.KSW_XBYTE, gaps)
+    for mm, e, _ in D.PACKED16_EDGES:
+        mat, gaps, items, xt = D.align_wave_split_case(mm, e)
+        for (q, t, _, _), x in zip(items, xt):
+            _both_align(q, t, mat, int(x), gaps)
+            _both_align(q, t, mat, int(x) ^ D.KSW_XBYTE, gaps)
+    for g in D.ALIGN_GAP_EDGES:
+        mat, gaps, items, xt = D.align_gap_edge_case(g)
+        for (q, t, _, _), x in zip(items, xt):
+            _both_align(q, t, mat, int(x), gaps)
+    for mat, items, want in D.align_i16_saturation_case():  # 16-bit saturation at 32767
+        for q, t, _, _ in items:
+            _both_align(q, t, mat, D.X_RESCUE, (6, 1, 6, 1))
+            _both_align(q, t, mat, D.KSW_XSTART, (6, 1, 6, 1))
+    mat = D.mat_abn(127, -128, -1)
+    for k, (q, t, _, _) in enumerate(D.align_items(1001, 60, qmax=200, tmax=300, related=0.9, copy=0.9)):
+        _both_align(q, t, mat, D.X_RESCUE | (D.KSW_XBYTE if k % 2 else 0), (6, 1, 6, 1))
+
+
+@pytest.mark.parametrize("name,gaps", [(n, (6, 1, 6, 1)) for n in sorted(D.ALIGN_MATS)] +
+                         [("3_5_1", (6, 1, 6, 11)), ("3_5_1", (6, 1, 6, 12)), ("2_8_2", (6, 1, 6, 12))])
+def test_ksw_align2_textbook_local_other_matrices(name, gaps):
+    """score / te / qe equal the textbook local alignment where the task does
+    not saturate (both widths)."""
+    mat = D.ALIGN_MATS[name]
+    items = D.align_items(1100 + len(name) + gaps[3], 36, qmax=90, tmax=260, related=0.9, mut=0.02, copy=0.9)
+    checked = 0
+    for k, (q, t, _, _) in enumerate(items):
+        x = D.X_RESCUE | (D.KSW_XBYTE if k % 2 else 0)
+        got = oracle_lib.ksw_align2(q, t, mat, x, *gaps)
+        if (x & D.KSW_XBYTE) and got[0] == 255:
+            continue
+        sc, te, qe = _textbook_local(list(q), list(t), mat, *gaps)
+        assert got[:3] == (sc, te, qe), (k, got, sc, te, qe)
+        checked += 1
+    assert checked >= len(items) // 2
+
+
+GLOBAL_XCHECK = [("default", D.DEFAULT_MAT)] + sorted(D.GLOBAL_LANE_OK_MATS.items()) + \
+    [("1_16_16", D.GLOBAL_U16_MATS["1_16_16"])]
+
+
+@pytest.mark.parametrize("gaps", D.GLOBAL_U16_GAPS)
+@pytest.mark.parametrize("mat_name,mat", GLOBAL_XCHECK, ids=[n for n, _ in GLOBAL_XCHECK])
+def test_global_other_matrices_vs_unbanded_dp_and_cigar(mat_name, mat, gaps):
+    """ksw_global2 == the unbanded DP when w >= max(qlen, tlen), and its
+    CIGAR's score equals its score, with -16 / -17 / 15 / 16 entries and the
+    three gap sets; and CIGAR consistency at the u16 edge's lengths.  (No
+    all-mismatch homopolymer pairs against the unbanded DP: their optimum is a
+    deletion next to an insertion, which bwa's recurrence, opening gaps from M
+    only, never takes, and which gotoh_global admits on its first row.)"""
+    rng = np.random.default_rng(13)
+    for k in range(16):
+        qlen = int(rng.integers(1, 60))
+        tlen = max(1, qlen + int(rng.integers(-6, 7)))
+        q, t = D.global_contents(rng, qlen, tlen, ("same", "related")[k % 2])
+        sc, cig = oracle_lib.ksw_global2(q, t, max(qlen, tlen), mat, *gaps)
+        assert sc == gotoh_global(list(q), list(t), mat, *gaps), (k, qlen, tlen)
+        assert cigar_score(cig, list(q), list(t), mat, *gaps) == sc, k
+    if mat_name in D.GLOBAL_U16_MATS:
+        p, b = D.global_u16_batches(mat_name, gaps)
+        for q, t, _, w in b["inside"] + b["outside"]:
+            sc, cig = oracle_lib.ksw_global2(q, t, w, mat, *gaps)
+            assert cigar_score(cig, list(q), list(t), mat, *gaps) == sc
+        q, t, _, _ = b["inside"][0]  # one task at the edge's full length against the unbanded DP
+        assert oracle_lib.ksw_global2(q, t, max(len(q), len(t)), mat, *gaps)[0] == \
+            gotoh_global(list(q), list(t), mat, *gaps)
+
+
+def test_global_grid_cigars_are_consistent():
+    """The NB-class grid (bands down to w = 0): wherever the band holds the
+    end cell (|qlen - tlen| <= w) the CIGAR's score equals the score."""
+    for mat in (D.DEFAULT_MAT, D.GLOBAL_U16_MATS["1_16_16"]):
+        n = 0
+        for q, t, _, w in D.global_grid_items():
+            sc, cig = oracle_lib.ksw_global2(q, t, w, mat)
+            if abs(len(q) - len(t)) <= w:
+                assert cigar_score(cig, list(q), list(t), mat) == sc, (len(q), len(t), w)
+                n += 1
+        assert n > 100
+
+
+@pytest.mark.parametrize("mat_name", sorted(D.EXT_GRID_MATS))
+def test_extend_grid_matches_independent_restatement(mat_name):
+    """Every fourth task of the column-class x score-form grid (and zdrop 0 /
+    end_bonus 0 on the default matrix)."""
+    mat = D.EXT_GRID_MATS[mat_name]
+    p, items = D.extend_grid_items(mat_name)
+    kws = [{}] + ([dict(zdrop=0), dict(end_bonus=0)] if mat_name == "default" else [])
+    for j, kw in enumerate(kws):
+        for q, t, h0, w in items[j::4 if not j else 16]:
+            ref, cells = oracle_lib.ksw_extend2(q, t, h0, w, mat, **kw)
+            got, gcells = py_extend(list(q), list(t), h0, w, mat, **kw)
+            assert ref == got and cells == gcells, (len(q), len(t), h0, w, kw, ref, got)
+
+
+@pytest.mark.parametrize("edge", ["bound_32000", "tlen_1024", "e_del_17", "e_ins_17", "pair_cg_129", "mat_min_17",
+                                  "mat_max_16"])
+def test_extend_edges_match_independent_restatement(edge):
+    for label, mat, kw, items in D.extend_edge_cases()[edge]:
+        for q, t, h0, w in items[::2]:
+            ref, cells = oracle_lib.ksw_extend2(q, t, h0, w, mat, **kw)
+            got, gcells = py_extend(list(q), list(t), h0, w, mat, **kw)
+            assert ref == got and cells == gcells, (edge, label, len(q), len(t), h0, w, ref, got)
