@@ -289,14 +289,15 @@ class SessionLease {
   }
   // An idle session whose arenas already hold `bytes` (host and device), or
   // false at once: no waiting, no session created, no arena grown.
-  bool try_acquire(int device, int kind, size_t bytes) {
+  bool try_acquire(int device, int kind, size_t bytes) { return try_acquire(device, kind, bytes, bytes); }
+  bool try_acquire(int device, int kind, size_t host_bytes, size_t dev_bytes) {
     release();
     SessionPool& P = session_pool(device, kind);
     std::lock_guard<std::mutex> lk(P.mu);
     if (P.releasing) return false;
     for (size_t i = 0; i < P.idle.size(); ++i) {
       Session* S = P.idle[i];
-      if (S->host_cap >= bytes && S->dev_cap >= bytes) {
+      if (S->host_cap >= host_bytes && S->dev_cap >= dev_bytes) {
         P.idle.erase(P.idle.begin() + (long)i);
         s_ = S;
         pool_ = &P;
@@ -1868,6 +1869,118 @@ int fcs_bgzf_inflate_try(const uint8_t* comp, int64_t comp_bytes, uint8_t* out, 
   return bgzf_inflate_host(comp, comp_bytes, out, out_cap, comp_used, out_bytes, device, true);
 }
 
+namespace {
+
+const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43,
+                              0x02, 0,    0x1b, 0,    0x03, 0, 0, 0, 0, 0, 0,    0, 0,    0};
+
+// fcs_bgzf_deflate / fcs_bgzf_deflate_try (`try_only`: an idle BGZF session
+// whose arenas already fit the call, or FCS_BGZF_BUSY).
+int bgzf_deflate_host(const uint8_t* data, int64_t n_bytes, int32_t block_bytes, int32_t eof, uint8_t* out,
+                      int64_t out_cap, int64_t* out_bytes, int64_t* coff, int32_t* n_members, int32_t device,
+                      bool try_only) {
+  if (!out_bytes || !n_members || n_bytes < 0 || (n_bytes > 0 && !data) || out_cap < 0 || (out_cap > 0 && !out))
+    return fail(FCS_ERR_INVALID, "[E::fcs_bgzf_deflate] bad arguments");
+  if (block_bytes < 1 || block_bytes > FCS_BGZF_BLOCK_MAX)
+    return fail(FCS_ERR_INVALID, "[E::fcs_bgzf_deflate] block_bytes " + std::to_string(block_bytes) + " outside 1.." +
+                                     std::to_string(FCS_BGZF_BLOCK_MAX));
+  *out_bytes = 0;
+  *n_members = 0;
+  const int64_t members = (n_bytes + block_bytes - 1) / block_bytes, tail = eof ? 28 : 0;
+  if (members > 0x7FFFFFFE)
+    return fail(FCS_ERR_INVALID, "[E::fcs_bgzf_deflate] " + std::to_string(members) + " members in one call");
+  if (members == 0) {
+    if (tail > out_cap)
+      return fail(FCS_ERR_INVALID, "[E::fcs_bgzf_deflate] output needs 28 bytes, capacity " + std::to_string(out_cap));
+    if (tail) std::memcpy(out, kBgzfEof, 28);
+    if (coff) coff[0] = 0;
+    *out_bytes = tail;
+    return FCS_OK;
+  }
+  int rc = check_device(device);
+  if (rc) return rc;
+  FCS_SET_DEVICE((device));
+  const size_t nm = (size_t)members;
+  // staged through the host arena: the input, the member starts, the compacted
+  // members; on the device alone: the member sizes and the 64 KiB slots
+  Layout L;
+  const size_t odata = L.add((size_t)n_bytes), ocoff = L.add(8 * (nm + 1));
+  const size_t oout = L.add((size_t)n_bytes + nm * 31);  // a member is at most its stored form: 18 + 5 + n + 8
+  const size_t host_bytes = L.total, oclen = L.add(4 * nm), oslots = L.add(nm * 65536);
+  SessionLease lease;
+  if (try_only) {
+    if (!lease.try_acquire(device, kInflateSession, host_bytes, L.total)) return FCS_BGZF_BUSY;
+  } else if ((rc = lease.acquire(device, kInflateSession))) {
+    return rc;
+  }
+  Session* S = lease.get();
+  if ((rc = S->ensure_host(host_bytes)) || (rc = S->ensure_dev(L.total))) return rc;
+  std::memcpy(S->h<void>(odata), data, (size_t)n_bytes);
+  hipStream_t s = S->s;
+  const StreamDrain drain{s};
+  FCS_HIP_CHECK(hipMemcpyAsync(S->d<void>(odata), S->h<void>(odata), (size_t)n_bytes, hipMemcpyHostToDevice, s));
+  if ((rc = launch_bgzf_deflate(S->d<uint8_t>(odata), n_bytes, block_bytes, S->d<uint8_t>(oslots), S->d<int32_t>(oclen), s)) ||
+      (rc = launch_bgzf_compact(S->d<uint8_t>(oslots), S->d<int32_t>(oclen), (int32_t)members, S->d<int64_t>(ocoff),
+                                S->d<uint8_t>(oout), s)))
+    return rc;
+  FCS_HIP_CHECK(hipMemcpyAsync(S->h<void>(ocoff), S->d<void>(ocoff), 8 * (nm + 1), hipMemcpyDeviceToHost, s));
+  if (!S->done) FCS_HIP_CHECK(hipEventCreateWithFlags(&S->done, hipEventBlockingSync | hipEventDisableTiming));
+  FCS_HIP_CHECK(hipEventRecord(S->done, s));
+  FCS_HIP_CHECK(hipEventSynchronize(S->done));
+  const int64_t* hc = S->h<int64_t>(ocoff);
+  for (size_t k = 0; k < nm; ++k)
+    if (hc[k + 1] - hc[k] < 28 || hc[k + 1] - hc[k] > 65536)  // a failed member counts 0 bytes
+      return fail(FCS_ERR_DEVICE, "[E::fcs_bgzf_deflate] member " + std::to_string(k) + " was not encoded");
+  const int64_t total = hc[nm];
+  if (total + tail > out_cap)
+    return fail(FCS_ERR_INVALID, "[E::fcs_bgzf_deflate] output needs " + std::to_string(total + tail) +
+                                     " bytes, capacity " + std::to_string(out_cap));
+  // one copy of the compressed bytes alone
+  FCS_HIP_CHECK(hipMemcpyAsync(S->h<void>(oout), S->d<void>(oout), (size_t)total, hipMemcpyDeviceToHost, s));
+  FCS_HIP_CHECK(hipEventRecord(S->done, s));
+  FCS_HIP_CHECK(hipEventSynchronize(S->done));
+  std::memcpy(out, S->h<void>(oout), (size_t)total);
+  if (tail) std::memcpy(out + total, kBgzfEof, 28);
+  if (coff) std::memcpy(coff, hc, 8 * (nm + 1));
+  *out_bytes = total + tail;
+  *n_members = (int32_t)members;
+  return FCS_OK;
+}
+
+}  // namespace
+
+int64_t fcs_bgzf_deflate_bound(int64_t n_bytes, int32_t block_bytes, int32_t eof) {
+  if (n_bytes < 0 || block_bytes < 1 || block_bytes > FCS_BGZF_BLOCK_MAX)
+    return fail(FCS_ERR_INVALID, "[E::fcs_bgzf_deflate_bound] bad arguments");
+  return (n_bytes + block_bytes - 1) / block_bytes * 65536 + (eof ? 28 : 0);
+}
+
+int fcs_bgzf_deflate(const uint8_t* data, int64_t n_bytes, int32_t block_bytes, int32_t eof, uint8_t* out,
+                     int64_t out_cap, int64_t* out_bytes, int64_t* coff, int32_t* n_members, int32_t device) {
+  return bgzf_deflate_host(data, n_bytes, block_bytes, eof, out, out_cap, out_bytes, coff, n_members, device, false);
+}
+
+int fcs_bgzf_deflate_try(const uint8_t* data, int64_t n_bytes, int32_t block_bytes, int32_t eof, uint8_t* out,
+                         int64_t out_cap, int64_t* out_bytes, int64_t* coff, int32_t* n_members, int32_t device) {
+  return bgzf_deflate_host(data, n_bytes, block_bytes, eof, out, out_cap, out_bytes, coff, n_members, device, true);
+}
+
+int fcs_bgzf_deflate_dev(const uint8_t* dev_data, int64_t n_bytes, int32_t block_bytes, uint8_t* dev_slots,
+                         int32_t* dev_clen, int32_t device, void* stream) {
+  if (n_bytes < 0 || (n_bytes > 0 && (!dev_data || !dev_slots || !dev_clen)) || ((uintptr_t)dev_slots & 3))
+    return fail(FCS_ERR_INVALID, "[E::fcs_bgzf_deflate_dev] bad arguments");
+  if (block_bytes < 1 || block_bytes > FCS_BGZF_BLOCK_MAX)
+    return fail(FCS_ERR_INVALID, "[E::fcs_bgzf_deflate_dev] block_bytes " + std::to_string(block_bytes) +
+                                     " outside 1.." + std::to_string(FCS_BGZF_BLOCK_MAX));
+  if ((n_bytes + block_bytes - 1) / block_bytes > 0x7FFFFFFE)
+    return fail(FCS_ERR_INVALID, "[E::fcs_bgzf_deflate_dev] too many members in one call");
+  if (n_bytes == 0) return FCS_OK;
+  int rc = check_device(device);
+  if (rc) return rc;
+  FCS_SET_DEVICE((device));
+  return launch_bgzf_deflate(dev_data, n_bytes, block_bytes, dev_slots, dev_clen, static_cast<hipStream_t>(stream));
+}
+
 int fcs_bgzf_warmup(int32_t device, int32_t sessions, int64_t arena_bytes) {
   if (sessions < 0 || arena_bytes < 0) return fail(FCS_ERR_INVALID, "[E::fcs_bgzf_warmup] bad arguments");
   int rc = check_device(device);
@@ -1934,6 +2047,6 @@ int fcs_device_release(int32_t device) {
   return FCS_OK;
 }
 
-int fcs_abi_symbol_count(void) { return 47; }
+int fcs_abi_symbol_count(void) { return 51; }
 
 }  // extern "C"

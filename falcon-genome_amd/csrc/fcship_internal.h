@@ -260,5 +260,12 @@ int launch_bsw_global(const BswDevBatch& b, const BswParams& p, int max_qlen, in
 // One wave per BGZF member (bgzf_kernels.hip); coff / uoff have n + 1 entries.
 int launch_bgzf_inflate(const uint8_t* comp, const int64_t* coff, const int64_t* uoff, int32_t n, uint8_t* out,
                         int32_t* status, hipStream_t s);
+// One wave per block of block_bytes input bytes (bgzf_deflate.hip): member k at
+// slots + k * 65536 (4-byte aligned), its size in clen[k] (-1: failed).
+int launch_bgzf_deflate(const uint8_t* data, int64_t n_bytes, int32_t block_bytes, uint8_t* slots, int32_t* clen,
+                        hipStream_t s);
+// coff[0..n] = prefix sums of clen, then member k's bytes to out + coff[k].
+int launch_bgzf_compact(const uint8_t* slots, const int32_t* clen, int32_t n, int64_t* coff, uint8_t* out,
+                        hipStream_t s);
 
 }  // namespace fcs

@@ -183,6 +183,13 @@ _sig("fcs_bgzf_inflate_try", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_in
 _sig("fcs_bgzf_warmup", C.c_int, [C.c_int32, C.c_int32, C.c_int64])
 _sig("fcs_bgzf_inflate_dev", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_int32, C.c_void_p])
+_sig("fcs_bgzf_deflate_bound", C.c_int64, [C.c_int64, C.c_int32, C.c_int32])
+_sig("fcs_bgzf_deflate", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, i64p,
+                                   C.c_void_p, i32p, C.c_int32])
+_sig("fcs_bgzf_deflate_try", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, i64p,
+                                       C.c_void_p, i32p, C.c_int32])
+_sig("fcs_bgzf_deflate_dev", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                       C.c_void_p])
 _sig("fcs_synth_phmm_sizes", C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, i64p, i64p])
 _sig("fcs_synth_phmm", C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 10)
 _sig("fcs_synth_bsw_sizes", C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
@@ -584,3 +591,22 @@ def bgzf_inflate(comp, out_cap: int | None = None, device: int = 0):
     used, got = C.c_int64(), C.c_int64()
     check(lib.fcs_bgzf_inflate(_ptr(c), len(c), out.ctypes.data, cap, C.byref(used), C.byref(got), device))
     return out[:got.value].tobytes(), used.value
+
+
+FCS_BGZF_BLOCK_MAX = 0xff00
+
+
+def bgzf_deflate(data, block_bytes: int = FCS_BGZF_BLOCK_MAX, eof: bool = False, device: int = 0):
+    """fcs_bgzf_deflate: (the BGZF members of `data` cut into blocks of
+    `block_bytes`, coff = the n + 1 member starts); `eof` appends the EOF
+    member (not in coff)."""
+    d = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+    cap = lib.fcs_bgzf_deflate_bound(len(d), block_bytes, int(eof))
+    if cap < 0:
+        check(int(cap))
+    out = np.zeros(max(cap, 1), np.uint8)
+    coff = np.zeros(cap // 65536 + 1, np.int64)
+    got, n = C.c_int64(), C.c_int32()
+    check(lib.fcs_bgzf_deflate(_ptr(d), len(d), block_bytes, int(eof), out.ctypes.data, cap, C.byref(got),
+                               coff.ctypes.data, C.byref(n), device))
+    return out[:got.value].tobytes(), coff[:n.value + 1].copy()

@@ -1632,6 +1632,7 @@ AlignStats align_fastq(const AlignJob& job, const std::vector<int>& devices, std
   h.text += "@PG\tID:fcs-genome\tPN:fcs-genome align\n";
   if (!job.disable_merge) {
     BamWriter w(job.output, h);
+    w.use_device(job.bgzf_device);
     w.index_on_close();
     std::vector<const BamRecord*> sorted(order.size());
     for (size_t i = 0; i < order.size(); ++i) sorted[i] = &recs[order[i].second];
@@ -1674,6 +1675,7 @@ AlignStats align_fastq(const AlignJob& job, const std::vector<int>& devices, std
     for (int k = 0; k < nb; ++k) {
       const std::string bam = get_contig_fname(job.output, k, "bam");
       BamWriter w(bam, h);
+      w.use_device(job.bgzf_device);
       w.index_on_close();
       w.write_all(per[k]);
       w.close();

@@ -132,6 +132,7 @@ AlignStats align_pairs(const Reference& ref, const KmerIndex& idx, const std::ve
 struct AlignJob {
   std::string ref_path, fq1, fq2, output;  // fq2 empty: single-end
   std::string rg = "sample", sample = "sample", platform = "illumina", library = "sample";
+  int bgzf_device = -1;        // >= 0: the BAM's blocks compress on that GPU (gpu.bgzf_deflate)
   bool disable_merge = false;  // bwa.num_buckets sorted bucket BAMs (+ .bai, .bed) in the directory `output`
 };
 

@@ -71,6 +71,7 @@ class BamWriter {
   // without reading the file back.
   void index_on_close() { index_ = true; }
   void close();
+  void use_device(int device) { bgzf_.use_device(device); }  // BgzfWriter::use_device (gpu.bgzf_deflate)
   uint64_t tell() { return bgzf_.tell(); }
 
  private:

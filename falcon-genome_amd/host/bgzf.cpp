@@ -150,6 +150,26 @@ std::vector<uint8_t> make_block(const uint8_t* data, size_t n, int level) {
   return {};
 }
 
+// The GPU deflate entry points of the loaded libfcship, looked up at run time:
+// a library without them (an older build, the CPU mock) leaves every writer on
+// the host codec.
+struct DeflateApi {
+  int64_t (*bound)(int64_t, int32_t, int32_t) = nullptr;
+  int (*deflate_try)(const uint8_t*, int64_t, int32_t, int32_t, uint8_t*, int64_t, int64_t*, int64_t*, int32_t*,
+                     int32_t) = nullptr;
+  bool ok() const { return bound && deflate_try; }
+};
+
+const DeflateApi& deflate_api() {
+  static const DeflateApi A = [] {
+    DeflateApi a;
+    a.bound = reinterpret_cast<decltype(a.bound)>(dlsym(RTLD_DEFAULT, "fcs_bgzf_deflate_bound"));
+    a.deflate_try = reinterpret_cast<decltype(a.deflate_try)>(dlsym(RTLD_DEFAULT, "fcs_bgzf_deflate_try"));
+    return a;
+  }();
+  return A;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ pool
@@ -225,21 +245,82 @@ BgzfWriter::~BgzfWriter() {
   }
 }
 
+void BgzfWriter::use_device(int device) {
+  if (device < 0 || !deflate_api().ok()) return;
+  submit_gather();
+  device_ = device;
+  // sessions whose arenas hold a batch (input, members, slots: about 3.1 times
+  // its bytes); a failure only leaves the batches to the host codec
+  (void)fcs_bgzf_warmup(device, 2, (int64_t)(4 * kBgzfDeviceBatch * kBgzfMaxBlock));
+  max_pending_ = std::max<size_t>(2, host_pool_size());
+}
+
 void BgzfWriter::emit_block(const uint8_t* data, size_t n) {
   ustarts_.push_back(ubytes_ - n);
-  std::vector<uint8_t> in(data, data + n);
   const int level = level_;
-  pending_.push_back(host_pool_async([in = std::move(in), level] { return make_block(in.data(), in.size(), level); }));
+  if (device_ >= 0) {
+    // a short block ends its batch: the call cuts its input every kBgzfBlockData bytes
+    gather_.insert(gather_.end(), data, data + n);
+    if (n != kBgzfBlockData || gather_.size() >= kBgzfDeviceBatch * kBgzfBlockData) submit_gather();
+  } else {
+    std::vector<uint8_t> in(data, data + n);
+    pending_.push_back(host_pool_async([in = std::move(in), level] {
+      Batch b;
+      b.bytes = make_block(in.data(), in.size(), level);
+      b.sizes.push_back((uint32_t)b.bytes.size());
+      return b;
+    }));
+  }
   drain(max_pending_);
 }
 
+void BgzfWriter::submit_gather() {
+  if (gather_.empty()) return;
+  std::vector<uint8_t> in = std::move(gather_);
+  gather_ = std::vector<uint8_t>();
+  const int level = level_, device = device_;
+  pending_.push_back(host_pool_async([in = std::move(in), level, device] {
+    Batch b;
+    b.gathered = true;
+    const DeflateApi& api = deflate_api();
+    const int64_t cap = api.bound((int64_t)in.size(), (int32_t)kBgzfBlockData, 0);
+    const size_t blocks = (in.size() + kBgzfBlockData - 1) / kBgzfBlockData;
+    if (cap > 0) {
+      b.bytes.resize((size_t)cap);
+      std::vector<int64_t> coff(blocks + 1);
+      int64_t got = 0;
+      int32_t n = 0;
+      const int rc = api.deflate_try(in.data(), (int64_t)in.size(), (int32_t)kBgzfBlockData, 0, b.bytes.data(), cap, &got,
+                                     coff.data(), &n, device);
+      if (rc == FCS_OK && (size_t)n == blocks) {
+        b.bytes.resize((size_t)got);
+        for (size_t k = 0; k < blocks; ++k) b.sizes.push_back((uint32_t)(coff[k + 1] - coff[k]));
+        b.on_device = true;
+        return b;
+      }
+    }
+    // busy (no warm session idle) or failed: this job's own core
+    b.bytes.clear();
+    for (size_t at = 0; at < in.size(); at += kBgzfBlockData) {
+      const std::vector<uint8_t> blk = make_block(in.data() + at, std::min(kBgzfBlockData, in.size() - at), level);
+      b.bytes.insert(b.bytes.end(), blk.begin(), blk.end());
+      b.sizes.push_back((uint32_t)blk.size());
+    }
+    return b;
+  }));
+}
+
 void BgzfWriter::drain(size_t keep) {
+  if (keep == 0) submit_gather();
   while (pending_.size() > keep) {
-    const std::vector<uint8_t> blk = pending_.front().get();
+    const Batch b = pending_.front().get();
     pending_.pop_front();
-    if (std::fwrite(blk.data(), 1, blk.size(), f_) != blk.size()) throw internalError("[E::bgzf] write failed");
-    coffs_.push_back(coff_);
-    coff_ += blk.size();
+    if (std::fwrite(b.bytes.data(), 1, b.bytes.size(), f_) != b.bytes.size()) throw internalError("[E::bgzf] write failed");
+    for (const uint32_t sz : b.sizes) {
+      coffs_.push_back(coff_);
+      coff_ += sz;
+    }
+    if (b.gathered) ++(b.on_device ? device_batches_ : host_batches_);
   }
 }
 
@@ -269,6 +350,10 @@ void BgzfWriter::close() {
     buf_.clear();
   }
   drain(0);
+  // FCS_BGZF_TRACE=1: where a device-mode writer's batches were compressed
+  if (device_ >= 0 && std::getenv("FCS_BGZF_TRACE"))
+    std::fprintf(stderr, "[bgzf_writer] device %d: %d batches on the GPU, %d on the host codec\n", device_,
+                 device_batches_, host_batches_);
   std::fwrite(kBgzfEof, 1, sizeof kBgzfEof, f_);
   std::fclose(f_);
   f_ = nullptr;

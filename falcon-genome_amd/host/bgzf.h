@@ -36,6 +36,7 @@ auto host_pool_async(F f) -> std::future<decltype(f())> {
 
 constexpr size_t kBgzfMaxBlock = 0x10000;   // max uncompressed bytes per block
 constexpr size_t kBgzfBlockData = 0xff00;   // what the writer packs per block (as htslib)
+constexpr size_t kBgzfDeviceBatch = 64;     // blocks per GPU deflate call of a writer in device mode (4 MiB)
 extern const uint8_t kBgzfEof[28];
 
 // Default deflate level of written BGZF (VCF.gz, BAM).  libdeflate level 5
@@ -62,6 +63,18 @@ class BgzfWriter {
     drain(0);
     return (coff_ << 16) | (uint64_t)buf_.size();
   }
+  // Device mode (gpu.bgzf_deflate): from the next block on, finished blocks
+  // are gathered, kBgzfDeviceBatch blocks at a time, and one pool job per
+  // batch sends them through fcs_bgzf_deflate_try to GPU `device` (SURVEY.md
+  // §8 row f3); a batch goes to the host codec when the call answers busy or
+  // fails.  Blocks keep their boundaries and their order, so block_offsets(),
+  // tell() and voffset() mean what they mean without it; only the compressed
+  // bytes differ.  Does nothing when the loaded libfcship has no deflate
+  // entry points (looked up at run time).
+  void use_device(int device);
+  // device mode: batches compressed on the GPU / by the host codec (complete after close())
+  int device_batches() const { return device_batches_; }
+  int host_batches() const { return host_batches_; }
   void close();  // flush + EOF block
   // Compressed start of every block written so far, in order (complete after
   // close()); with no flush() between writes, block k holds the uncompressed
@@ -89,8 +102,17 @@ class BgzfWriter {
   bool uniform_ = true;  // every block but the last holds kBgzfBlockData bytes (voffset by division)
   // blocks compress on the host pool and are written in order; tell() first
   // writes every pending block
-  std::deque<std::future<std::vector<uint8_t>>> pending_;
+  struct Batch {
+    std::vector<uint8_t> bytes;   // whole members, in order
+    std::vector<uint32_t> sizes;  // of each
+    bool gathered = false, on_device = false;  // a device-mode batch; compressed on the GPU
+  };
+  void submit_gather();  // device mode: the gathered blocks become a pending batch
+  std::deque<std::future<Batch>> pending_;
   size_t max_pending_ = 0;
+  int device_ = -1;
+  std::vector<uint8_t> gather_;  // device mode: whole blocks not yet submitted (only the last may be short)
+  int device_batches_ = 0, host_batches_ = 0;
 };
 
 class BgzfReader {

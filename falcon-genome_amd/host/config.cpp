@@ -54,6 +54,8 @@ void Config::init(const std::string& root_dir) {
           "a shard whose PairHMM pass finds the GPU runtime still coming up runs a queued shard meanwhile");
   declare("gpu.bam_inflate", "false",
           "inflate a calling window's BAM blocks on the GPU (fcs_bgzf_inflate) instead of host libdeflate");
+  declare("gpu.bgzf_deflate", "false",
+          "compress the final VCF.gz's and align's BAM blocks on the GPU (fcs_bgzf_deflate) instead of host libdeflate");
   // caller knobs (GATK HaplotypeCaller / Mutect2 argument defaults)
   declare("htc.min_base_quality", "10", "min base quality counted as evidence of activity");
   declare("htc.base_quality_threshold", "18", "PairHMM: base quals below this become 6");

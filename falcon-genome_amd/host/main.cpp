@@ -111,6 +111,14 @@ std::vector<int> slots() {
   return g;
 }
 
+// gpu.bgzf_deflate: the device the final VCF.gz's blocks compress on (the first slot's), or -1.
+int bgzf_device(const std::vector<int>& gpus) {
+  if (!conf().get_bool("gpu.bgzf_deflate")) return -1;
+  for (int d : gpus)
+    if (d >= 0) return d;
+  return -1;
+}
+
 // Shards of the run: -L list (one file for all shards) or the reference's 32 interval parts.
 std::vector<std::vector<std::string>> shard_intervals(const std::string& ref, const std::string& intv_list) {
   const int n = conf().get_int("gatk.ncontigs");
@@ -234,11 +242,14 @@ int htc_main(int argc, char** argv) {
   if (!a.has("skip-concat")) {
     if (!force && path_exists(plain + ".gz")) throw invalidParam("output " + plain + ".gz exists (use -f)");
     // concat -> bgzip -> tabix as one pass over the parts
-    ex.addTask(std::make_shared<VCFConcatWorker>(parts, plain, plain + ".gz", /*consume=*/true), sample_id, true);
+    ex.addTask(std::make_shared<VCFConcatWorker>(parts, plain, plain + ".gz", /*consume=*/true, bgzf_device(gpus)),
+               sample_id, true);
   } else {
     ex.addTask(std::make_shared<VCFConcatWorker>(parts, plain), sample_id, true);
   }
-  if (conf().get_bool("gpu.release_early")) ex.addTask(std::make_shared<GpuReleaseWorker>(gpus, &warm), sample_id);
+  // with gpu.bgzf_deflate the tail compresses on a device: the release waits for it (a stage of its own)
+  if (conf().get_bool("gpu.release_early"))
+    ex.addTask(std::make_shared<GpuReleaseWorker>(gpus, &warm), sample_id, bgzf_device(gpus) >= 0);
   timeline("stages queued");
   ex.run();
   timeline("stages done");
@@ -289,8 +300,10 @@ int mutect2_main(int argc, char** argv) {
                                                true),
                sample_id);
   }
-  ex.addTask(std::make_shared<VCFConcatWorker>(parts, output, output + ".gz", /*consume=*/true), sample_id, true);
-  if (conf().get_bool("gpu.release_early")) ex.addTask(std::make_shared<GpuReleaseWorker>(gpus, &warm), sample_id);
+  ex.addTask(std::make_shared<VCFConcatWorker>(parts, output, output + ".gz", /*consume=*/true, bgzf_device(gpus)),
+             sample_id, true);
+  if (conf().get_bool("gpu.release_early"))
+    ex.addTask(std::make_shared<GpuReleaseWorker>(gpus, &warm), sample_id, bgzf_device(gpus) >= 0);
   ex.run();
   warm.wait();
   if (warm.status() != 0) throw failedCommand(std::string("[E::fcs-genome] GPU warm-up failed: ") + fcs_last_error());

@@ -346,7 +346,7 @@ namespace {
 // BgzfReader's tell() reports.
 class BgzipIndexer {
  public:
-  explicit BgzipIndexer(std::string gz) : gz_(std::move(gz)), w_(gz_) {}
+  explicit BgzipIndexer(std::string gz, int bgzf_device = -1) : gz_(std::move(gz)), w_(gz_) { w_.use_device(bgzf_device); }
   // lines [a, b) of *buf (b ends a line, or the data); parsed in pieces of
   // about kPiece bytes so one large part still spreads over the pool
   void add(std::shared_ptr<const std::vector<char>> buf, size_t a, size_t b) {
@@ -459,7 +459,7 @@ void bgzip_tabix_file(const std::string& input, const std::string& output) {
 }
 
 void vcf_concat_bgzip_tabix(const std::vector<std::string>& inputs, const std::string& plain, const std::string& gz,
-                            bool consume_inputs) {
+                            bool consume_inputs, int bgzf_device) {
   // vcf_concat's text (every line of the first part, the others without
   // their '#' lines, a last line without '\n' gets one) written to `plain`
   // and, in the same pass, bgzipped + indexed as bgzip_tabix_file(plain, gz)
@@ -477,7 +477,7 @@ void vcf_concat_bgzip_tabix(const std::vector<std::string>& inputs, const std::s
       ::close(fd);
     }
   } po{fd, {}};
-  BgzipIndexer bx(gz);
+  BgzipIndexer bx(gz, bgzf_device);
   // the next part loads on the pool while this one is written
   auto load = [](const std::string& path) {
     return host_pool_async([path] {

@@ -61,8 +61,9 @@ void bgzip_tabix_file(const std::string& input, const std::string& output);
 // the parts (HTC's concat → bgzip → tabix tail as one stage).
 // consume_inputs: each input file is removed once it has been read (temporary
 // shard parts; their pages leave the page cache inside this pass instead of in
-// a separate removal afterwards).
+// a separate removal afterwards).  bgzf_device >= 0: the .gz's blocks compress on
+// that GPU (BgzfWriter::use_device, gpu.bgzf_deflate).
 void vcf_concat_bgzip_tabix(const std::vector<std::string>& inputs, const std::string& plain, const std::string& gz,
-                            bool consume_inputs = false);
+                            bool consume_inputs = false, int bgzf_device = -1);
 
 }  // namespace fcsg

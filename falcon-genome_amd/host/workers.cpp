@@ -182,12 +182,14 @@ int Mutect2Worker::run(TaskContext& ctx) {
 }
 
 // ------------------------------------------------------------------ VCF tail
-VCFConcatWorker::VCFConcatWorker(std::vector<std::string> inputs, std::string output, std::string gz, bool consume)
+VCFConcatWorker::VCFConcatWorker(std::vector<std::string> inputs, std::string output, std::string gz, bool consume,
+                                 int bgzf_device)
     : Worker(1, 1, {}, gz.empty() ? "VCF concat" : "VCF concat + bgzip + tabix"),
       inputs_(std::move(inputs)),
       output_(std::move(output)),
       gz_(std::move(gz)),
-      consume_(consume) {}
+      consume_(consume),
+      bgzf_device_(bgzf_device) {}
 
 void VCFConcatWorker::check() {
   if (inputs_.empty()) throw invalidParam("no VCF to concatenate");
@@ -195,7 +197,7 @@ void VCFConcatWorker::check() {
 
 int VCFConcatWorker::run(TaskContext&) {
   if (gz_.empty()) vcf_concat(inputs_, output_);
-  else vcf_concat_bgzip_tabix(inputs_, output_, gz_, consume_);
+  else vcf_concat_bgzip_tabix(inputs_, output_, gz_, consume_, bgzf_device_);
   return 0;
 }
 
@@ -268,6 +270,9 @@ int BWAWorker::run(TaskContext& ctx) {
   job.platform = platform_id_;
   job.library = library_id_;
   job.disable_merge = !flag_merge_bams_;
+  if (conf().get_bool("gpu.bgzf_deflate"))
+    for (int d : gpus_)
+      if (d >= 0 && job.bgzf_device < 0) job.bgzf_device = d;
   std::string report;
   align_fastq(job, gpus_, report);
   if (ctx.log) std::fputs(report.c_str(), ctx.log);

@@ -65,7 +65,9 @@ class VCFConcatWorker : public Worker {
  public:
   // gz non-empty: also gz + gz.tbi from the same pass (concat + bgzip + tabix as one stage);
   // consume: the inputs are temporary parts, removed as soon as they are read
-  VCFConcatWorker(std::vector<std::string> inputs, std::string output, std::string gz = "", bool consume = false);
+  // bgzf_device >= 0: the .gz's blocks compress on that GPU (gpu.bgzf_deflate)
+  VCFConcatWorker(std::vector<std::string> inputs, std::string output, std::string gz = "", bool consume = false,
+                  int bgzf_device = -1);
   void check() override;
   int run(TaskContext& ctx) override;
 
@@ -73,6 +75,7 @@ class VCFConcatWorker : public Worker {
   std::vector<std::string> inputs_;
   std::string output_, gz_;
   bool consume_;
+  int bgzf_device_;
 };
 
 class ZIPWorker : public Worker {

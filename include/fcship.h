@@ -85,8 +85,8 @@ int fcs_stream_release(int32_t device, void* stream);
  * calls it beside the VCF tail.  FCS_ERR_INVALID while a synchronous
  * (host-pointer) call on the device is still running; while the reset runs,
  * such calls on the device fail with FCS_ERR_INVALID (fcs_bgzf_inflate_try
- * answers FCS_BGZF_BUSY).  The *_dev entry points on caller streams and plans
- * the caller owns are not tracked: the caller finishes them first.  A later
+ * and fcs_bgzf_deflate_try answer FCS_BGZF_BUSY).  The *_dev entry points on
+ * caller streams and plans the caller owns are not tracked: the caller finishes them first.  A later
  * call on the device sets everything up again.
  * The reset frees every allocation of the process on the device, other
  * libraries' included: call it only when nothing else holds device memory. */
@@ -390,6 +390,39 @@ int fcs_bgzf_inflate_dev(const uint8_t* dev_comp, const int64_t* dev_coff, const
 int fcs_bgzf_inflate_try(const uint8_t* comp, int64_t comp_bytes, uint8_t* out, int64_t out_cap, int64_t* comp_used,
                          int64_t* out_bytes, int32_t device);
 int fcs_bgzf_warmup(int32_t device, int32_t sessions, int64_t arena_bytes);
+
+/* ------------------------------------------------------ BGZF deflate (§8 f3) */
+/* The writing side (htslib bgzf.c deflate_block: `fcs-genome` bgzips its VCF
+ * and writes BAM): data[0, n_bytes) is cut into blocks of block_bytes (1 ..
+ * FCS_BGZF_BLOCK_MAX; the last block shorter) and every block becomes one
+ * BGZF member on the GPU: the 18-byte header with the BC field, a raw-DEFLATE
+ * payload (LZ77 matches, the smallest of a stored, a fixed-code and a
+ * dynamic-code block), CRC-32 and ISIZE.  A member's bytes depend on its
+ * block's bytes alone.  No input, no member.
+ *
+ * fcs_bgzf_deflate_bound: bytes that always suffice for out (members * 65536,
+ * + 28 with eof); FCS_ERR_INVALID (negative) on bad arguments.
+ *
+ * fcs_bgzf_deflate: host buffers, synchronous; the members concatenated into
+ * out, *out_bytes their size, coff (nullable) the *n_members + 1 member
+ * starts; eof != 0 appends the 28-byte EOF member (not counted in
+ * *n_members).  FCS_ERR_INVALID when out_cap is smaller than what is
+ * produced (nothing is written then).
+ *
+ * fcs_bgzf_deflate_try: the same without waiting: FCS_BGZF_BUSY (nothing
+ * written) unless a warm BGZF session (fcs_bgzf_warmup) is idle whose staging
+ * arenas already hold the call.
+ *
+ * fcs_bgzf_deflate_dev: device buffers, stream-ordered, no sync: member k at
+ * dev_slots + k * 65536 (dev_slots 4-byte aligned), its size in dev_clen[k]. */
+#define FCS_BGZF_BLOCK_MAX 0xff00
+int64_t fcs_bgzf_deflate_bound(int64_t n_bytes, int32_t block_bytes, int32_t eof);
+int fcs_bgzf_deflate(const uint8_t* data, int64_t n_bytes, int32_t block_bytes, int32_t eof, uint8_t* out,
+                     int64_t out_cap, int64_t* out_bytes, int64_t* coff, int32_t* n_members, int32_t device);
+int fcs_bgzf_deflate_try(const uint8_t* data, int64_t n_bytes, int32_t block_bytes, int32_t eof, uint8_t* out,
+                         int64_t out_cap, int64_t* out_bytes, int64_t* coff, int32_t* n_members, int32_t device);
+int fcs_bgzf_deflate_dev(const uint8_t* dev_data, int64_t n_bytes, int32_t block_bytes, uint8_t* dev_slots,
+                         int32_t* dev_clen, int32_t device, void* stream);
 
 /* ---------------------------------------------- synthetic workload builders */
 /* Seeded generators for the benchmark configurations (BASELINE.json C2/C3).
