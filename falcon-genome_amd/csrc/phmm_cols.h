@@ -30,12 +30,25 @@
 // fill or drain inside a stream, only at its end (15 steps per stream).
 // Per cell the arithmetic is phmm3's exactly (same operations, same order),
 // so the results are bitwise those of the row-streamed kernel.
-// phmm5_kernel (below) is the same kernel with one pair stream per register
-// instead of two packed half-streams, and phmm4_kernel is kept as its bitwise
-// reference (FCSHIP_COLS=packed).  phmm6_kernel (at the end) runs phmm5's step
-// on streams that never end inside a class: a persistent grid takes pair after
-// pair from a per-class queue.  It is the one every class launches, and
-// phmm5_kernel is its bitwise reference (FCSHIP_COLS=single).
+// Three kernels follow.  phmm4_kernel is the one described above, two packed
+// half-streams per register; it stands alone and is kept as the bitwise
+// reference of the other two (FCSHIP_COLS=packed).  phmm5_kernel and
+// phmm6_kernel carry one pair stream per register and share one stream body,
+// cols1_stream<C, Feed>: tables, code fetch, capture, ring stages, the 16-step
+// block with the step arithmetic and the result write.  Each kernel adds only
+// how pairs reach the streams:
+//   * phmm5_kernel (FCSHIP_COLS=single): the batch loop over the workgroups,
+//     the prefix-scan segment table of a batch, and Cols1Batch (pair k in lane
+//     k, K pairs per stream, a fixed number of steps);
+//   * phmm6_kernel (the one every class launches): the first dequeue and the
+//     early exit, and Cols1Queue (the circular segment table filled from a
+//     per-class queue by a persistent grid, streams that end when the class
+//     is exhausted).
+// That the two compute the same bits per step is therefore structural: there
+// is one step.  What the tests hold equal is the rest: the stream mechanics of
+// phmm6 against phmm5 on the same batch (tests/test_pairhmm_queue_gpu.py), and
+// the shared step against phmm4's independent one (there and in
+// tests/test_pairhmm_single_gpu.py).
 #pragma once
 
 namespace fcs {
@@ -554,7 +567,8 @@ __global__ __launch_bounds__(64, 2) void phmm4_kernel(
   }
 }
 
-// ---- phmm5: the same kernel with ONE pair stream per register.
+// ---- phmm5 and phmm6: the same kernel with ONE pair stream per register
+// (constants and ring layout here, the body and the two kernels below).
 // phmm4 is pinned at 2 waves per SIMD by its registers (195 .. 249 VGPRs) and
 // a packed f32 op issues in the time of its two scalar halves, so packing buys
 // no issue rate and costs the occupancy.  Here a segment carries one stream:
@@ -592,330 +606,54 @@ __device__ __forceinline__ void cols1_put(unsigned char* smem, int slot, int seg
   *reinterpret_cast<pu2*>(p + 4 * kCols1ChunkBytes) = pu2{c.tlo, c.thi | (c.z != 0.f ? 0x01000000u : 0u)};
 }
 
-template <int C>
-__global__ __launch_bounds__(64, cols1_waves(C)) void phmm5_kernel(
-    const PhmmDevBatch b, const int32_t* __restrict__ order, const int64_t* __restrict__ bounds, const int cls,
-    const int K, const int tail_pairs, const PhmmTables<float> gtab, double* __restrict__ out,
-    int32_t* __restrict__ rescue_list, unsigned long long* __restrict__ rescue_count, const float thr,
-    const int use_rescue, int32_t* __restrict__ fb_list, unsigned long long* __restrict__ fb_count) {
-  constexpr int NW = (C + 3) / 4;  // code dwords
+// ---- The single-stream body, shared by phmm5_kernel and phmm6_kernel (DESIGN
+// §4.1h).  cols1_stream<C, Feed> (below) runs a wave's four streams: the
+// segment-table accessors, the code fetch, the capture, the ring's two stages
+// and prologue, the 16-step block with the step arithmetic, and the result
+// write exist once.  What a kernel adds is its Feed, the way pairs reach the
+// streams: which lane of the segment table holds pair k (slot), whether pair
+// k is there (valid, in cols1_stream), when the next pair's codes may be
+// converted, and when the streams end.
+constexpr int kNever = 0x3FFFFFFF;  // a stream row that never comes
+
+// One entry of a segment table: lane sl of a segment holds the pair of slot
+// sl of that segment's stream, G = the pair's first stream row.
+struct Cols1Seg {
+  int pm, Rm, Hm, Gm;
+  int64_t rom, hom;
+  float Im;
+};
+
+// The match tables copied to LDS for the ring items (every lane of the wave calls it).
+__device__ __forceinline__ PhmmTables<float> cols1_tables(const PhmmTables<float>& gtab) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
-  const int lane = threadIdx.x;
-  const int seg = lane >> 4;
-  const int sl = lane & 15;  // lane of the segment, and its entry of the segment table: pair sl of the stream
-  const int sbase = lane & 48;
-  const int i0 = sl * C;  // first haplotype index of this lane's columns
-  const int64_t cbeg = bounds[cls];
-  const long long count = bounds[cls + 1] - cbeg;
-  order += cbeg;
   PhmmTables<float> tab = gtab;
-  {
-    float* const t = reinterpret_cast<float*>(smem_raw + kCols1TabOff);
-    for (int i = lane; i < 128; i += 64) {
-      t[i] = gtab.ph2pr[i];
-      t[128 + i] = gtab.dmatch[i];
-      t[256 + i] = gtab.dmis[i];
-    }
-    tab.ph2pr = t;
-    tab.dmatch = t + 128;
-    tab.dmis = t + 256;
+  float* const t = reinterpret_cast<float*>(smem_raw + kCols1TabOff);
+  for (int i = threadIdx.x; i < 128; i += 64) {
+    t[i] = gtab.ph2pr[i];
+    t[128 + i] = gtab.dmatch[i];
+    t[256 + i] = gtab.dmis[i];
   }
-  // Batches: 4 streams per wave, K pairs each, except the range's last
-  // tail_pairs (shortest haplotypes), one pair per stream.
-  const long long tailn = count < (long long)tail_pairs ? count : (long long)tail_pairs;
-  const long long headn = count - tailn;
-  const long long per = 4LL * K;
-  const long long nb_head = (headn + per - 1) / per;
-  const long long nbatch = nb_head + (tailn + 3) / 4;
-
-  for (long long w = blockIdx.x; w < nbatch; w += gridDim.x) {
-    const bool head = w < nb_head;
-    const int Kb = head ? K : 1;
-    const long long bstart = head ? w * per : headn + (w - nb_head) * 4;
-    const long long bend = head ? min(headn, bstart + per) : min(count, bstart + 4);
-    // Segment table: lane sl holds pair sl of the segment's stream (stream seg
-    // of the batch takes every 4th pair).
-    const long long idx = bstart + seg + 4LL * sl;
-    const int pm = (sl < Kb && idx < bend) ? order[idx] : -1;
-    int Rm = 0, Hm = 0;
-    int64_t rom = 0, hom = 0;
-    float Im = 0.f;
-    if (pm >= 0) {
-      const int ri = b.pair_read[pm], hi = b.pair_hap[pm];
-      Rm = b.read_len[ri];
-      Hm = b.hap_len[hi];
-      rom = b.read_off[ri];
-      hom = b.hap_off[hi];
-      Im = tab.init_const / (float)Hm;
-    }
-    const int len = pm >= 0 ? Rm + 2 : 0;  // rows 1..R, V, Z
-    int incl = len;
-#pragma unroll
-    for (int d = 1; d < 16; d <<= 1) {
-      const int v = __shfl_up(incl, d, 16);
-      if (sl >= d) incl += v;
-    }
-    const int Gm = incl - len;  // first stream row of the pair
-    const int tot = __builtin_amdgcn_ds_bpermute(4 * (sbase + 15), incl);
-    const int nsteps = ((wave_max(tot) + 15) + 15) & ~15;
-    int sb = sbase * 4;  // laundered once per block, as in phmm4
-    auto bp = [&](int v, int k) { return __builtin_amdgcn_ds_bpermute(sb + 4 * min(k, 15), v); };
-    auto tG = [&](int k) { return bp(Gm, k); };
-    auto tR = [&](int k) { return bp(Rm, k); };
-    auto tH = [&](int k) { return bp(Hm, k); };
-    auto tP = [&](int k) { return bp(pm, k); };
-    auto tI = [&](int k) { return __int_as_float(bp(__float_as_int(Im), k)); };
-    auto t64 = [&](int64_t v, int k) {
-      const int lo = bp((int)v, k), hi = bp((int)(v >> 32), k);
-      return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-    };
-    auto valid = [&](int k) {  // the shuffle runs in every lane whatever k is
-      const int pv = tP(k);
-      return k < Kb && pv >= 0;
-    };
-
-    // Haplotype codes: cur (in use), nxt (the stream's next pair, taken by
-    // lane l at stream row swr, i.e. step swr + l), nk = the pair held in nxt.
-    // other: bit k = pair k has a haplotype byte outside A/C/G/T/N.
-    uint32_t cur[NW], nxt[NW];
-    int nk, swr;
-    unsigned other = 0u;
-    auto fetch_codes = [&](int k, uint32_t (&dst)[NW]) {  // uniform: every lane of the wave calls it
-      const bool ok = valid(k);
-      const int Hk = tH(k);
-      const int H = ok ? Hk : 0;
-      const int64_t ho = t64(hom, k);
-      uint32_t raw[NW + 1];
-      int al;
-      cols_load<NW>(b.hb, ok ? ho : 0, H, i0, raw, al);
-      bool oth = false;
-      cols_convert<NW>(raw, al, i0, H, dst, oth);
-      const unsigned long long bal = __ballot(oth && ok);
-      if (((bal >> sbase) & 0xFFFFull) != 0ull) other |= 1u << k;
-    };
-#pragma unroll
-    for (int d = 0; d < NW; ++d) cur[d] = 0x06060606u;
-    fetch_codes(0, nxt);
-    nk = 0;
-    swr = valid(0) ? tG(0) : 0x3FFFFFFF;
-    // Capture: lane 15 takes the sum at the V row of pair kc.
-    int kc = 0, cap, capp;
-    auto load_cap = [&] {
-      const bool ok = valid(kc);
-      const int v = tG(kc) + tR(kc);
-      cap = ok ? v : -0x3FFFFFFF;  // stream row of the V row
-      capp = tP(kc);
-    };
-    load_cap();
-
-    // The ring's items (row base + sl per lane) in two stages one block apart.
-    int kp = 0;  // stage A's cursor: the pair holding this lane's item row
-    RawRow praw{-1, 0, 0, 0, 0, 0, 0};
-    int prole = 0;  // role | first << 4
-    float pih = 0.f;
-    bool kok = false, nok = false;
-    int kG = 0, kR = 0, nG = 0;
-    float kI = 0.f;
-    int64_t kro = 0;
-    auto load_cursor = [&] {
-      kok = valid(kp);
-      kG = tG(kp);
-      kR = tR(kp);
-      kI = tI(kp);
-      kro = t64(rom, kp);
-      nok = valid(kp + 1);
-      nG = tG(kp + 1);
-    };
-    load_cursor();
-    auto stage_a = [&](int base) {
-      const int g = base + sl;
-      const bool adv = nok && g >= nG;  // pairs span >= 35 rows: at most one advance per 16 rows
-      if (__ballot(adv) != 0ull) {
-        if (adv) ++kp;
-        load_cursor();
-      }
-      const int r = g - kG;
-      int role = 0;
-      if (kok && r >= 0 && r < kR) role = r == kR - 1 ? 3 : 2;
-      else if (kok && r == kR) role = 4;
-      pih = kI;
-      prole = role | (r == 0 ? 16 : 0);
-      praw = (role == 2 || role == 3) ? load_raw(b, kR, kro, r) : RawRow{-1, 0, 0, 0, 0, 0, 0};
-    };
-    auto stage_b = [&](int base) {  // base >= 0
-      cols1_put(smem_raw, (int)((unsigned)(base + sl) % (unsigned)kCols1Ring), seg,
-                cols_item(tab, praw, prole & 15, (prole & 16) != 0, pih));
-    };
-    {  // ring prologue: rows -16..-1 are Z (slots 32..47), rows 0..15 built, rows 16..31 requested
-      cols1_put(smem_raw, 32 + sl, seg, cols_item(tab, RawRow{-1, 0, 0, 0, 0, 0, 0}, 0, false, 0.f));
-      stage_a(0);
-      stage_b(0);
-      stage_a(16);
-    }
-
-    float Xn[C], In[C];
-#pragma unroll
-    for (int j = 0; j < C; ++j) {
-      Xn[j] = 1.f;
-      In[j] = 0.f;
-    }
-    float dn = 1.f, xo = 1.f, xin = 1.f;
-    const uint32_t segoff = (uint32_t)seg * (kCols1Ring * 8u) + lds_addr(smem_raw);
-
-    for (int t0 = 0; t0 < nsteps; t0 += 16) {
-      asm volatile("" : "+v"(sb));
-      // Next pair's codes: once every lane took the pair in nxt (lane 15 reached
-      // row swr before this block), convert the one after it.  The block starts
-      // at most 31 rows after swr and the next pair at swr + R + 2 >= swr + 35.
-      {
-        const bool ev = swr + 16 <= t0 && nk + 1 < Kb;
-        if (__ballot(ev) != 0ull) {  // uniform: fetch_codes shuffles
-          uint32_t tmp[NW];
-          fetch_codes(nk + 1, tmp);
-          const bool vn = valid(nk + 1);
-          const int gn = tG(nk + 1);
-          if (ev) {
-#pragma unroll
-            for (int d = 0; d < NW; ++d) nxt[d] = tmp[d];
-            ++nk;
-            swr = vn ? gn : 0x3FFFFFFF;
-          }
-        }
-        if (swr + 16 <= t0 && nk + 1 >= Kb) swr = 0x3FFFFFFF;  // last pair taken
-      }
-      // The ring's rows t0 + 16 .. t0 + 31 (slots of rows t0 - 32 .. t0 - 17,
-      // read last in the previous block), requested one block ago; then the
-      // requests for rows t0 + 32 .. t0 + 47.
-      stage_b(t0 + 16);
-      stage_a(t0 + 32);
-      {
-        const bool adv = cap >= 0 && cap + 15 < t0;  // lane 15 passed the V row in an earlier block
-        if (__ballot(adv) != 0ull) {
-          if (adv) ++kc;
-          load_cap();
-        }
-      }
-      const bool capo = (other >> kc) & 1u;
-      const int gb = t0 - sl;  // this lane's row at the block's first step
-      const bool any_cap = __ballot(sl == 15 && (unsigned)(cap - gb) < 16u) != 0ull;
-      // steps of this block at which some lane takes its next haplotype codes
-      // (lane l of segment q switches at step swr - t0 + l): a uniform 16-bit mask
-      unsigned swmask = 0u;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int lo = __builtin_amdgcn_readlane(swr, 16 * q) - t0;  // steps lo .. lo + 15
-        if (lo < 16 && lo + 15 >= 0) {
-          const int a = max(lo, 0), bnd = min(lo + 15, 15);
-          swmask |= ((2u << bnd) - 1u) & ~((1u << a) - 1u);
-        }
-      }
-      uint32_t xs = ((uint32_t)(gb + kCols1Ring) % (uint32_t)kCols1Ring) * 8u;  // gb >= -15
-      uint32_t capa = lds_addr(smem_raw) + kCols1CapOff + seg * 64;
-      int g0 = gb;
-
-#pragma nounroll
-      for (int pass = 0; pass < 2; ++pass) {
-        auto step = [&](auto S_) {
-          constexpr int S = decltype(S_)::value;
-          const int g = g0 + S;
-          if (swmask & (1u << S)) {  // uniform
-            const bool take = g == swr;
-#pragma unroll
-            for (int d = 0; d < NW; ++d) {
-              uint32_t r;
-              asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(cur[d]), "v"(nxt[d]), "s"(__ballot(take)));
-              cur[d] = r;
-            }
-          }
-          asm volatile("" ::: "memory");
-          const uint32_t a0 = xs + (uint32_t)(S * 8);  // < 2 * 48 * 8: one subtraction wraps
-          const uint32_t pa = min(a0, a0 - (uint32_t)(kCols1Ring * 8)) + segoff;
-          auto ld2 = [&](int chunk) {
-            return *reinterpret_cast<const __attribute__((address_space(3))) pf2*>((uintptr_t)(pa + chunk * kCols1ChunkBytes));
-          };
-          const pf2 r0 = ld2(0), r1 = ld2(1), r2 = ld2(2), r3 = ld2(3);
-          const pu2 cr = *reinterpret_cast<const __attribute__((address_space(3))) pu2*>((uintptr_t)(pa + 4 * kCols1ChunkBytes));
-          const float e1 = r0.x, e3 = r0.y, my = r1.x, yy = r1.y, mm = r2.x, gm = r2.y, mx = r3.x, xx = r3.y;
-          const float z = (float)(cr.y >> 24);  // v_cvt_f32_ubyte3: 1 on Z rows
-          // the lane below's D into column l*C + 1 (lane 0: 1 on Z rows, else
-          // 0) and its X(g, l*C) for the next row (lane 0: X(g, 0) = 1 after a Z row)
-          const float din = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(z), __float_as_int(dn), kDppRowShr1, 0xF, 0xF, false));
-          const float xnx = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(z), __float_as_int(xo), kDppRowShr1, 0xF, 0xF, false));
-          const float xcur = xin;
-          xin = xnx;
-          uint32_t mA = 0;
-          auto prior = [&](int j, const float dep) {  // tied to the previous column's D, as in phmm4
-            if ((j & 3) == 0) mA = __builtin_amdgcn_perm(cr.y, cr.x, cur[j >> 2]);
-            int a;
-            asm volatile("v_bfe_i32 %0, %1, %2, 1" : "=v"(a) : "v"(mA), "i"(8 * (j & 3)), "v"(dep));
-            return sel_v((uint32_t)a, e1, e3);
-          };
-          float Mn = xcur * prior(0, xcur);
-          float D = din, Mp = 0.f, Dp = 0.f;
-#pragma unroll
-          for (int j = 0; j < C; ++j) {
-            const float M = Mn;
-            if (j > 0) D = __builtin_fmaf(Mp, my, Dp * yy);
-            float I = In[j], Xo = Xn[j];
-            asm volatile("" : "+v"(I), "+v"(Xo) : "v"(D));
-            if (j + 1 < C) Mn = Xo * prior(j + 1, D);
-            float xn = __builtin_fmaf(M, mm, __builtin_fmaf(I, gm, D));
-            float in = __builtin_fmaf(M, mx, I * xx);
-            asm volatile("" : "+v"(xn), "+v"(in));
-            Xn[j] = xn;
-            In[j] = in;
-            Mp = M;
-            Dp = D;
-          }
-          dn = __builtin_fmaf(Mp, my, Dp * yy);
-          xo = Xn[C - 1];
-          // lane 15's D entering column 16 C + 1, kept per step in LDS: at a V
-          // row it is the stream's sum, taken after the block
-          uint64_t keep;
-          const uint32_t cpa = capa + 0u;
-          const float dnv = dn;
-          asm volatile(
-              "s_mov_b64 %0, exec\n\t"
-              "s_mov_b64 exec, %3\n\t"
-              "ds_write_b32 %1, %2 offset:%4\n\t"
-              "s_mov_b64 exec, %0"
-              : "=&s"(keep)
-              : "v"(cpa), "v"(dnv), "s"(kTopLanes), "i"(4 * S)
-              : "memory");
-        };
-        [&]<int... S>(std::integer_sequence<int, S...>) {
-          (step(std::integral_constant<int, S>{}), ...);
-        }(std::make_integer_sequence<int, 8>{});
-        g0 += 8;
-        swmask >>= 8;
-        capa += 32;
-        xs += 64;
-        xs = min(xs, xs - (uint32_t)(kCols1Ring * 8));
-      }
-      if (any_cap) {
-        // lane 15 at a V row: the D entering column 16 C + 1 is the stream's sum
-        if (sl == 15 && (unsigned)(cap - gb) < 16u) {
-          const float acc = *reinterpret_cast<const float*>(smem_raw + kCols1CapOff + seg * 64 + 4 * (cap - gb));
-          const int p = capp;
-          if (capo) {
-            const unsigned long long k = atomicAdd(fb_count, 1ull);
-            fb_list[k] = p;
-            out[p] = __builtin_nan("");
-          } else if (use_rescue && acc < thr) {
-            const unsigned long long k = atomicAdd(rescue_count, 1ull);
-            rescue_list[k] = p;
-            out[p] = __builtin_nan("");
-          } else {
-            out[p] = (double)(log10f(acc) - tab.log10_init);
-          }
-        }
-      }
-    }
-  }
+  tab.ph2pr = t;
+  tab.dmatch = t + 128;
+  tab.dmis = t + 256;
+  return tab;
 }
 
-// ---- phmm6: phmm5's step on CONTINUOUS streams fed from a per-class queue
-// (DESIGN §4.1g).  A class launch is one round of the chip (CUs x 4 SIMDs x 3
+// phmm5's feed: a batch.  The table is filled before the streams start: pair k
+// of a stream in lane k, Kb pairs at most (k past them reads lane 15, which
+// `valid` rejects), and the streams end after nsteps steps.
+struct Cols1Batch {
+  static constexpr bool kQueue = false;
+  int Kb, nsteps;
+  static __device__ __forceinline__ int slot(int k) { return min(k, 15); }
+  static __device__ __forceinline__ int bit(int k) { return k; }
+  __device__ __forceinline__ bool more(int t0) const { return t0 < nsteps; }
+  __device__ __forceinline__ bool done(int) const { return false; }
+};
+
+// ---- phmm6's feed: CONTINUOUS streams fed from a per-class queue (DESIGN
+// §4.1g).  A class launch is one round of the chip (CUs x 4 SIMDs x 3
 // waves, each a workgroup), and a wave's four streams run until the class is
 // exhausted: no batches, so no drain, no ring prologue and no segment-table
 // scan between pairs, no one-pair tail, and no workgroups that find nothing.
@@ -941,82 +679,42 @@ __global__ __launch_bounds__(64, cols1_waves(C)) void phmm5_kernel(
 //     (it arrives >= 32 rows before its G) and its codes are converted.
 //   * When the queue is empty a stream runs out its pairs and feeds Z rows;
 //     the wave ends at the block top after its last capture.
-// The step body is phmm5's: the same operations on the same operands in the
-// same order, so every output is bitwise phmm5's.
+// The streams run in cols1_stream; this is its feed.
 constexpr int kCols6Lds = kCols1Lds;
 constexpr int kCols6Waves = 3;   // per SIMD: the grid is CUs x 4 x kCols6Waves workgroups
 constexpr int kCols6Ahead = 48;  // rows located ahead of stage A below which a stream asks for its next pair
 static_assert(kCols6Lds <= 13653, "12 waves per CU");
 
-template <int C>
-__global__ __launch_bounds__(64, kCols6Waves) void phmm6_kernel(
-    const PhmmDevBatch b, const int32_t* __restrict__ order, const int64_t* __restrict__ bounds, const int cls,
-    const PhmmTables<float> gtab, double* __restrict__ out, int32_t* __restrict__ rescue_list,
-    unsigned long long* __restrict__ rescue_count, const float thr, const int use_rescue,
-    int32_t* __restrict__ fb_list, unsigned long long* __restrict__ fb_count,
-    unsigned long long* __restrict__ qhead) {
-  constexpr int NW = (C + 3) / 4;  // code dwords
-  constexpr int kNever = 0x3FFFFFFF;
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  const int lane = threadIdx.x;
-  const int seg = lane >> 4;
-  const int sl = lane & 15;  // lane of the segment, and its slot of the circular segment table
-  const int sbase = lane & 48;
-  const int i0 = sl * C;  // first haplotype index of this lane's columns
-  const int64_t cbeg = bounds[cls];
-  const long long count = bounds[cls + 1] - cbeg;
-  order += cbeg;
-  // The wave's first dequeue: one pair per stream.  pend = the streams with a
-  // request in flight (wave-uniform), qv = lane 0's answer: the first position
-  // of the class handed to this request (its low 32 bits: a class has fewer
-  // than 2^31 pairs and every stream overshoots the end at most once).
-  unsigned pend = 0xFu;
-  uint32_t qv = 0u;
-  if (lane == 0) qv = (uint32_t)atomicAdd(qhead, 4ull);
-  // a wave that finds its class exhausted leaves before it touches LDS
-  if ((long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)qv) >= count) return;
-  PhmmTables<float> tab = gtab;
-  {
-    float* const t = reinterpret_cast<float*>(smem_raw + kCols1TabOff);
-    for (int i = lane; i < 128; i += 64) {
-      t[i] = gtab.ph2pr[i];
-      t[128 + i] = gtab.dmatch[i];
-      t[256 + i] = gtab.dmis[i];
-    }
-    tab.ph2pr = t;
-    tab.dmatch = t + 128;
-    tab.dmis = t + 256;
-  }
-
-  // Segment table: lane sl holds the stream's pair number n with n mod 16 = sl.
-  int pm = -1, Rm = 0, Hm = 0, Gm = 0;
-  int64_t rom = 0, hom = 0;
-  float Im = 0.f;
+struct Cols1Queue {
+  static constexpr bool kQueue = true;
+  const int32_t* order;  // the class's pairs
+  long long count;
+  unsigned long long* qhead;
+  // pend = the streams with a request in flight (wave-uniform), qv = lane 0's
+  // answer: the first position of the class handed to this request (its low
+  // 32 bits: a class has fewer than 2^31 pairs and every stream overshoots
+  // the end at most once).
+  unsigned pend;
+  uint32_t qv;
   // Stream state (the same in every lane of a segment): nq = pairs taken so
   // far (pair numbers 0 .. nq - 1 are in the table or done), gend = the stream
   // row after the last taken pair's Z row, closed = the queue had no pair left
-  // for this stream.  other: bit n mod 16 = pair n has a haplotype byte
-  // outside A/C/G/T/N.
+  // for this stream.
   int nq = 0, gend = 0;
   bool closed = false;
-  unsigned other = 0u;
-  int sb = sbase * 4;  // laundered once per block, as in phmm4
-  auto bp = [&](int v, int k) { return __builtin_amdgcn_ds_bpermute(sb + 4 * (k & 15), v); };
-  auto tG = [&](int k) { return bp(Gm, k); };
-  auto tR = [&](int k) { return bp(Rm, k); };
-  auto tH = [&](int k) { return bp(Hm, k); };
-  auto tP = [&](int k) { return bp(pm, k); };
-  auto tI = [&](int k) { return __int_as_float(bp(__float_as_int(Im), k)); };
-  auto t64 = [&](int64_t v, int k) {
-    const int lo = bp((int)v, k), hi = bp((int)(v >> 32), k);
-    return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-  };
-  auto valid = [&](int k) { return k >= 0 && k < nq; };
+  static __device__ __forceinline__ int slot(int k) { return k & 15; }
+  static __device__ __forceinline__ int bit(int k) { return k & 15; }
+  __device__ __forceinline__ bool more(int) const { return true; }
+  // every stream closed and its last pair captured: the wave is done
+  __device__ __forceinline__ bool done(int kc) const { return __ballot(!closed || kc < nq) == 0ull; }
   // The answer to the request in flight (uniform: every lane calls it): the
   // streams of `pend`, in stream order, take positions qv, qv + 1, ..; a
   // position past the class closes the stream.  The pair starts at row
-  // max(gend, gmin), gmin = the first row stage A has not located.
-  auto complete = [&](int gmin) {
+  // max(gend, gmin), gmin = the first row stage A has not located, in slot
+  // nq mod 16 of the table, whose `other` bit it clears.
+  __device__ __forceinline__ void complete(int gmin, const PhmmDevBatch& b, const PhmmTables<float>& tab, Cols1Seg& tb,
+                                           unsigned& other) {
+    const int seg = threadIdx.x >> 4, sl = threadIdx.x & 15;
     const long long base = (long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)qv);
     const bool mine = (pend >> seg) & 1u;
     const long long idx = base + __popc(pend & ((1u << seg) - 1u));
@@ -1028,38 +726,88 @@ __global__ __launch_bounds__(64, kCols6Waves) void phmm6_kernel(
       const int R = b.read_len[ri], H = b.hap_len[hi];
       const int G = max(gend, gmin);
       if (sl == (nq & 15)) {
-        pm = p;
-        Rm = R;
-        Hm = H;
-        rom = b.read_off[ri];
-        hom = b.hap_off[hi];
-        Im = tab.init_const / (float)H;
-        Gm = G;
+        tb.pm = p;
+        tb.Rm = R;
+        tb.Hm = H;
+        tb.rom = b.read_off[ri];
+        tb.hom = b.hap_off[hi];
+        tb.Im = tab.init_const / (float)H;
+        tb.Gm = G;
       }
       other &= ~(1u << (nq & 15));
       gend = G + R + 2;  // rows 1..R, V, Z
       ++nq;
     }
     pend = 0u;
+  }
+  // One request, at a block top, for every stream that has fewer than
+  // kCols6Ahead located rows left ahead of stage A (kc: the capture cursor).
+  __device__ __forceinline__ void request(int t0, int kc) {
+    const bool need = !closed && gend < t0 + 32 + kCols6Ahead && nq - kc < 8;
+    const unsigned long long bal = __ballot(need && (threadIdx.x & 15) == 0);
+    if (bal != 0ull) {  // uniform
+      pend = (unsigned)((bal & 1ull) | ((bal >> 15) & 2ull) | ((bal >> 30) & 4ull) | ((bal >> 45) & 8ull));
+      qv = 0u;
+      if (threadIdx.x == 0) qv = (uint32_t)atomicAdd(qhead, (unsigned long long)__popc(pend));
+    }
+  }
+};
+
+// The streams of one wave: tb = this lane's entry of its segment's table (a
+// batch's, or empty for a queue, which fills it), tab = cols1_tables().
+template <int C, class Feed>
+__device__ __forceinline__ void cols1_stream(const PhmmDevBatch& b, const PhmmTables<float>& tab, Cols1Seg tb,
+                                             Feed feed, double* __restrict__ out,
+                                             int32_t* __restrict__ rescue_list,
+                                             unsigned long long* __restrict__ rescue_count, const float thr,
+                                             const int use_rescue, int32_t* __restrict__ fb_list,
+                                             unsigned long long* __restrict__ fb_count) {
+  constexpr int NW = (C + 3) / 4;  // code dwords
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const int lane = threadIdx.x;
+  const int seg = lane >> 4;
+  const int sl = lane & 15;  // lane of the segment, and its slot of the segment table
+  const int sbase = lane & 48;
+  const int i0 = sl * C;  // first haplotype index of this lane's columns
+  int sb = sbase * 4;  // laundered once per block, as in phmm4
+  auto bp = [&](int v, int k) { return __builtin_amdgcn_ds_bpermute(sb + 4 * Feed::slot(k), v); };
+  auto tG = [&](int k) { return bp(tb.Gm, k); };
+  auto tR = [&](int k) { return bp(tb.Rm, k); };
+  auto tH = [&](int k) { return bp(tb.Hm, k); };
+  auto tP = [&](int k) { return bp(tb.pm, k); };
+  auto tI = [&](int k) { return __int_as_float(bp(__float_as_int(tb.Im), k)); };
+  auto t64 = [&](int64_t v, int k) {
+    const int lo = bp((int)v, k), hi = bp((int)(v >> 32), k);
+    return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
+  };
+  auto valid = [&](int k) {
+    if constexpr (Feed::kQueue) {
+      return k >= 0 && k < feed.nq;
+    } else {  // the shuffle runs in every lane whatever k is
+      const int pv = tP(k);
+      return k < feed.Kb && pv >= 0;
+    }
   };
 
   // Haplotype codes: cur (in use), nxt (the stream's next pair, taken by lane
   // l at stream row swr, i.e. step swr + l; kNever: every lane has taken it),
-  // nk = the pair held in nxt.
+  // nk = the pair held in nxt.  other: bit Feed::bit(k) = pair k has a
+  // haplotype byte outside A/C/G/T/N.
   uint32_t cur[NW], nxt[NW];
   int nk = -1, swr = kNever;
+  unsigned other = 0u;
   auto fetch_codes = [&](int k, uint32_t (&dst)[NW]) {  // uniform: every lane of the wave calls it
     const bool ok = valid(k);
     const int Hk = tH(k);
     const int H = ok ? Hk : 0;
-    const int64_t ho = t64(hom, k);
+    const int64_t ho = t64(tb.hom, k);
     uint32_t raw[NW + 1];
     int al;
     cols_load<NW>(b.hb, ok ? ho : 0, H, i0, raw, al);
     bool oth = false;
     cols_convert<NW>(raw, al, i0, H, dst, oth);
     const unsigned long long bal = __ballot(oth && ok);
-    if (((bal >> sbase) & 0xFFFFull) != 0ull) other |= 1u << (k & 15);
+    if (((bal >> sbase) & 0xFFFFull) != 0ull) other |= 1u << Feed::bit(k);
   };
 #pragma unroll
   for (int d = 0; d < NW; ++d) cur[d] = nxt[d] = 0x06060606u;
@@ -1086,7 +834,7 @@ __global__ __launch_bounds__(64, kCols6Waves) void phmm6_kernel(
     kG = tG(kp);
     kR = tR(kp);
     kI = tI(kp);
-    kro = t64(rom, kp);
+    kro = t64(tb.rom, kp);
     nok = valid(kp + 1);
     nG = tG(kp + 1);
   };
@@ -1109,11 +857,19 @@ __global__ __launch_bounds__(64, kCols6Waves) void phmm6_kernel(
     cols1_put(smem_raw, (int)((unsigned)(base + sl) % (unsigned)kCols1Ring), seg,
               cols_item(tab, praw, prole & 15, (prole & 16) != 0, pih));
   };
-  {  // the streams' first pairs start at row 0; ring prologue as in phmm5:
-     // rows -16..-1 are Z (slots 32..47), rows 0..15 built, rows 16..31 requested
-    complete(0);
-    load_cursor();
-    load_cap();
+  // The streams' first pairs start at row 0: a queue's come with the answer
+  // to the wave's first request, a batch's are in the table and their codes
+  // are converted here.
+  if constexpr (Feed::kQueue) {
+    feed.complete(0, b, tab, tb, other);
+  } else {
+    fetch_codes(0, nxt);
+    nk = 0;
+    swr = valid(0) ? tG(0) : kNever;
+  }
+  load_cursor();
+  load_cap();
+  {  // ring prologue: rows -16..-1 are Z (slots 32..47), rows 0..15 built, rows 16..31 requested
     cols1_put(smem_raw, 32 + sl, seg, cols_item(tab, RawRow{-1, 0, 0, 0, 0, 0, 0}, 0, false, 0.f));
     stage_a(0);
     stage_b(0);
@@ -1129,43 +885,45 @@ __global__ __launch_bounds__(64, kCols6Waves) void phmm6_kernel(
   float dn = 1.f, xo = 1.f, xin = 1.f;
   const uint32_t segoff = (uint32_t)seg * (kCols1Ring * 8u) + lds_addr(smem_raw);
 
-  for (int t0 = 0;; t0 += 16) {
+  for (int t0 = 0; feed.more(t0); t0 += 16) {
     asm volatile("" : "+v"(sb));
     // The queue.  The pairs asked for one block ago start at the first row
     // stage A has not located (t0 + 32) or after the stream's last pair; then
-    // one request for every stream that has fewer than kCols6Ahead located
-    // rows left ahead of stage A.
-    if (pend != 0u) {  // uniform
-      complete(t0 + 32);
-      load_cursor();
-      load_cap();
-    }
-    {
-      const bool need = !closed && gend < t0 + 32 + kCols6Ahead && nq - kc < 8;
-      const unsigned long long bal = __ballot(need && sl == 0);
-      if (bal != 0ull) {  // uniform
-        pend = (unsigned)((bal & 1ull) | ((bal >> 15) & 2ull) | ((bal >> 30) & 4ull) | ((bal >> 45) & 8ull));
-        qv = 0u;
-        if (lane == 0) qv = (uint32_t)atomicAdd(qhead, (unsigned long long)__popc(pend));
+    // the next request.
+    if constexpr (Feed::kQueue) {
+      if (feed.pend != 0u) {  // uniform
+        feed.complete(t0 + 32, b, tab, tb, other);
+        load_cursor();
+        load_cap();
       }
+      feed.request(t0, kc);
     }
     // Next pair's codes: once every lane took the pair in nxt (lane 15 reached
-    // row swr before this block), convert the one after it as soon as it is
-    // in the table.
+    // row swr before this block), convert the one after it: a batch's at once
+    // (the block starts at most 31 rows after swr and the next pair at swr +
+    // R + 2 >= swr + 35), a queue's as soon as it is in the table.
     {
-      if (swr != kNever && swr + 16 <= t0) swr = kNever;
-      const bool ev = swr == kNever && nk + 1 < nq;
+      bool ev;
+      if constexpr (Feed::kQueue) {
+        if (swr != kNever && swr + 16 <= t0) swr = kNever;
+        ev = swr == kNever && nk + 1 < feed.nq;
+      } else {
+        ev = swr + 16 <= t0 && nk + 1 < feed.Kb;
+      }
       if (__ballot(ev) != 0ull) {  // uniform: fetch_codes shuffles
         uint32_t tmp[NW];
         fetch_codes(nk + 1, tmp);
+        const bool vn = valid(nk + 1);
         const int gn = tG(nk + 1);
         if (ev) {
 #pragma unroll
           for (int d = 0; d < NW; ++d) nxt[d] = tmp[d];
           ++nk;
-          swr = gn;
+          swr = vn ? gn : kNever;
         }
       }
+      if constexpr (!Feed::kQueue)
+        if (swr + 16 <= t0 && nk + 1 >= feed.Kb) swr = kNever;  // last pair taken
     }
     // The ring's rows t0 + 16 .. t0 + 31 (slots of rows t0 - 32 .. t0 - 17,
     // read last in the previous block), requested one block ago; then the
@@ -1179,9 +937,8 @@ __global__ __launch_bounds__(64, kCols6Waves) void phmm6_kernel(
         load_cap();
       }
     }
-    // every stream closed and its last pair captured: the wave is done
-    if (__ballot(!closed || kc < nq) == 0ull) break;
-    const bool capo = (other >> (kc & 15)) & 1u;
+    if (feed.done(kc)) break;
+    const bool capo = (other >> Feed::bit(kc)) & 1u;
     const int gb = t0 - sl;  // this lane's row at the block's first step
     const bool any_cap = __ballot(sl == 15 && (unsigned)(cap - gb) < 16u) != 0ull;
     // steps of this block at which some lane takes its next haplotype codes
@@ -1297,6 +1054,83 @@ __global__ __launch_bounds__(64, kCols6Waves) void phmm6_kernel(
       }
     }
   }
+}
+
+// phmm5: batches.  A workgroup runs batch after batch: 4 streams per wave, K
+// pairs each, except the range's last tail_pairs (shortest haplotypes), one
+// pair per stream.  Every batch fills its segment tables and pays the ring
+// prologue and the 15-step drain.
+template <int C>
+__global__ __launch_bounds__(64, cols1_waves(C)) void phmm5_kernel(
+    const PhmmDevBatch b, const int32_t* __restrict__ order, const int64_t* __restrict__ bounds, const int cls,
+    const int K, const int tail_pairs, const PhmmTables<float> gtab, double* __restrict__ out,
+    int32_t* __restrict__ rescue_list, unsigned long long* __restrict__ rescue_count, const float thr,
+    const int use_rescue, int32_t* __restrict__ fb_list, unsigned long long* __restrict__ fb_count) {
+  const int lane = threadIdx.x;
+  const int seg = lane >> 4;
+  const int sl = lane & 15;
+  const int sbase = lane & 48;
+  const int64_t cbeg = bounds[cls];
+  const long long count = bounds[cls + 1] - cbeg;
+  order += cbeg;
+  const PhmmTables<float> tab = cols1_tables(gtab);
+  const long long tailn = count < (long long)tail_pairs ? count : (long long)tail_pairs;
+  const long long headn = count - tailn;
+  const long long per = 4LL * K;
+  const long long nb_head = (headn + per - 1) / per;
+  const long long nbatch = nb_head + (tailn + 3) / 4;
+
+  for (long long w = blockIdx.x; w < nbatch; w += gridDim.x) {
+    const bool head = w < nb_head;
+    const int Kb = head ? K : 1;
+    const long long bstart = head ? w * per : headn + (w - nb_head) * 4;
+    const long long bend = head ? min(headn, bstart + per) : min(count, bstart + 4);
+    // Segment table: lane sl holds pair sl of the segment's stream (stream seg
+    // of the batch takes every 4th pair).
+    const long long idx = bstart + seg + 4LL * sl;
+    Cols1Seg tb{(sl < Kb && idx < bend) ? order[idx] : -1, 0, 0, 0, 0, 0, 0.f};
+    if (tb.pm >= 0) {
+      const int ri = b.pair_read[tb.pm], hi = b.pair_hap[tb.pm];
+      tb.Rm = b.read_len[ri];
+      tb.Hm = b.hap_len[hi];
+      tb.rom = b.read_off[ri];
+      tb.hom = b.hap_off[hi];
+      tb.Im = tab.init_const / (float)tb.Hm;
+    }
+    const int len = tb.pm >= 0 ? tb.Rm + 2 : 0;  // rows 1..R, V, Z
+    int incl = len;
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1) {
+      const int v = __shfl_up(incl, d, 16);
+      if (sl >= d) incl += v;
+    }
+    tb.Gm = incl - len;  // first stream row of the pair
+    const int tot = __builtin_amdgcn_ds_bpermute(4 * (sbase + 15), incl);
+    const int nsteps = ((wave_max(tot) + 15) + 15) & ~15;
+    cols1_stream<C>(b, tab, tb, Cols1Batch{Kb, nsteps}, out, rescue_list, rescue_count, thr, use_rescue, fb_list,
+                    fb_count);
+  }
+}
+
+// phmm6: one persistent wave per workgroup, its streams fed by Cols1Queue.
+template <int C>
+__global__ __launch_bounds__(64, kCols6Waves) void phmm6_kernel(
+    const PhmmDevBatch b, const int32_t* __restrict__ order, const int64_t* __restrict__ bounds, const int cls,
+    const PhmmTables<float> gtab, double* __restrict__ out, int32_t* __restrict__ rescue_list,
+    unsigned long long* __restrict__ rescue_count, const float thr, const int use_rescue,
+    int32_t* __restrict__ fb_list, unsigned long long* __restrict__ fb_count,
+    unsigned long long* __restrict__ qhead) {
+  const int64_t cbeg = bounds[cls];
+  const long long count = bounds[cls + 1] - cbeg;
+  // The wave's first dequeue: one pair per stream.
+  uint32_t qv = 0u;
+  if (threadIdx.x == 0) qv = (uint32_t)atomicAdd(qhead, 4ull);
+  // a wave that finds its class exhausted leaves before it touches LDS
+  if ((long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)qv) >= count) return;
+  const PhmmTables<float> tab = cols1_tables(gtab);
+  // The segment table starts empty: lane sl will hold the stream's pair number n with n mod 16 = sl.
+  cols1_stream<C>(b, tab, Cols1Seg{-1, 0, 0, 0, 0, 0, 0.f}, Cols1Queue{order + cbeg, count, qhead, 0xFu, qv}, out,
+                  rescue_list, rescue_count, thr, use_rescue, fb_list, fb_count);
 }
 
 }  // namespace fcs

@@ -613,15 +613,22 @@ static int launch_one(const PhmmDevBatch& b, const int32_t* order, const unsigne
   return FCS_OK;
 }
 
+// FCSHIP_STREAM_K (tests), read once; <= 0: not forced.  Each kernel's pairs-
+// per-stream function clamps it to its own maximum.
+static int forced_stream_k() {
+  static const int forced = [] {
+    const char* e = std::getenv("FCSHIP_STREAM_K");
+    return e ? std::atoi(e) : 0;
+  }();
+  return forced;
+}
+
 // Pairs per segment stream of the streamed kernel: as many as keep >= ~24K
 // waves in flight for the batch (8 x 3 waves x 256 CUs x 4 SIMDs), at most
 // kStreamMaxK (a stream's quantisation loss is < 1/2 stripe in K pairs).
 // FCSHIP_STREAM_K=k (tests) forces k pairs per stream on any batch size.
 static int stream_pairs_per_segment(int64_t n) {
-  static const int forced = [] {
-    const char* e = std::getenv("FCSHIP_STREAM_K");
-    return e ? std::atoi(e) : 0;
-  }();
+  const int forced = forced_stream_k();
   if (forced > 0) return std::min(forced, kStreamMaxK);
   const int64_t k = n / (4 * 24576);
   return (int)std::max<int64_t>(1, std::min<int64_t>(kStreamMaxK, k));
@@ -631,10 +638,7 @@ static int stream_pairs_per_segment(int64_t n) {
 // waves in flight for the batch (8 half-streams per wave), at most 8.
 // FCSHIP_STREAM_K=k (tests) forces k here too.
 static int cols_pairs_per_half(int64_t n) {
-  static const int forced = [] {
-    const char* e = std::getenv("FCSHIP_STREAM_K");
-    return e ? std::atoi(e) : 0;
-  }();
+  const int forced = forced_stream_k();
   if (forced > 0) return std::min(forced, 8);
   const int64_t k = n / (8 * 24576);
   return (int)std::max<int64_t>(1, std::min<int64_t>(8, k));
@@ -647,10 +651,7 @@ static int cols_pairs_per_half(int64_t n) {
 // (tests) forces k here too, and then shrinks the one-pair-per-stream tail to
 // a single batch so that test-sized classes run k-pair streams at all.
 static int cols1_forced_k() {
-  static const int forced = [] {
-    const char* e = std::getenv("FCSHIP_STREAM_K");
-    return e ? std::atoi(e) : 0;
-  }();
+  const int forced = forced_stream_k();
   return forced > 0 ? std::min(forced, kCols1MaxK) : 0;
 }
 static int cols1_pairs_per_stream(int64_t n) {

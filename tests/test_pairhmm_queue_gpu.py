@@ -1,7 +1,10 @@
 """The queue-fed column kernel (phmm6, phmm_cols.h) bitwise against the
 single-stream column kernel (phmm5) on the same batch, and against the oracle.
+phmm5 and phmm6 share their stream body (cols1_stream), so each batch's
+`single` run is in turn held bitwise to the packed kernel (phmm4), which shares
+no code with them.
 
-FCSHIP_COLS=queue|single forces either kernel for every column class and
+FCSHIP_COLS=queue|single|packed forces one kernel for every column class and
 FCSHIP_QUEUE_WAVES caps the workgroups of a queue launch (1: one wave works
 through the whole class, so each of its four streams runs a quarter of the
 class's pairs back to back and refills the slots of its circular segment
@@ -99,11 +102,17 @@ def check_queue_against_single(path, p, waves, ref=None):
     """The queue run inside the oracle's parity bar, bitwise the single-stream
     kernel's outputs with and without the rescue (NaN patterns included), the
     same rescued set and rescue count.  ref: the batch's `single` run, if it
-    was made already.  Returns (out, the single run)."""
+    was made already; when it is made here, it is checked bitwise (outputs and
+    rescue count) against a `packed` run.  Returns (out, the single run)."""
     src = save_batch(path, p)
     if ref is None:
         d = child(CHILD, src, path / "single.npz", "single", 0)
         ref = d["out"], d["raw"], int(d["rescued"])
+        # phmm5 and phmm6 share their step; phmm4 (packed) shares no code with them
+        d = child(CHILD, src, path / "packed.npz", "packed", 0)
+        assert same_bits(d["raw"], ref[1]), np.flatnonzero(d["raw"].view(np.uint64) != ref[1].view(np.uint64))[:8]
+        assert same_bits(d["out"], ref[0]), np.flatnonzero(d["out"].view(np.uint64) != ref[0].view(np.uint64))[:8]
+        assert int(d["rescued"]) == ref[2], (int(d["rescued"]), ref[2])
     d = child(CHILD, src, path / f"queue_{waves}.npz", "queue", waves)
     out, raw, n = d["out"], d["raw"], int(d["rescued"])
     sout, sraw, sn = ref
@@ -235,7 +244,8 @@ def test_queue_counter_reset(gpu, tmp_path):
     """Plan API on a 300-pair batch: schedule, forward twice, schedule and
     forward again.  A queue head left over from the previous pass would leave
     pairs unwritten (the sentinel survives); all three outputs are bit-equal,
-    hold no sentinel, and match the single-stream kernel's."""
+    hold no sentinel, and match the single-stream kernel's and the packed
+    kernel's."""
     rng = np.random.default_rng(6300)
     haps = [rng.choice(np.frombuffer(b"ACGT", np.uint8), H) for H in (180, 240, 290)]
     reads = []
@@ -258,4 +268,6 @@ def test_queue_counter_reset(gpu, tmp_path):
     assert same_bits(res[0], res[1]) and same_bits(res[0], res[2])
     assert cnt[0] > 0 and cnt[0] == cnt[1] == cnt[2], cnt
     assert same_bits(res[0], s["res"][0]) and cnt[0] == s["cnt"][0]
+    k = child(CHILD_PLAN, src, tmp_path / "plan_packed.npz", "packed", 0)
+    assert same_bits(res[0], k["res"][0]) and cnt[0] == k["cnt"][0]
     check_parity(p, res[0], False)
