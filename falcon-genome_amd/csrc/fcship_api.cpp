@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "fcship_internal.h"
+#include "fmd_smem.h"
 
 namespace fcs {
 
@@ -1981,6 +1982,294 @@ int fcs_bgzf_deflate_dev(const uint8_t* dev_data, int64_t n_bytes, int32_t block
   return launch_bgzf_deflate(dev_data, n_bytes, block_bytes, dev_slots, dev_clen, static_cast<hipStream_t>(stream));
 }
 
+}  // extern "C"
+
+// ------------------------------------------------------------ FMD-index seeding
+// A device copy of an FMD-index.  Live handles are registered, so a call can
+// tell a handle that was never made, destroyed, or lost its device memory to
+// fcs_device_release from a good one before it touches the device.
+struct fcs_fmd_index {
+  int device = 0;
+  bool released = false;  // fcs_device_release reset the device: the pointers are gone
+  FmdDevIndex dx{};
+  void* mem[4] = {nullptr, nullptr, nullptr, nullptr};  // occ, C, sa, special
+};
+
+namespace {
+
+std::mutex g_fmd_mu;
+auto* g_fmd_live = new std::map<const fcs_fmd_index*, fcs_fmd_index*>();  // outlives static teardown
+
+// The registered handle behind `h`, or null (with the error set).
+const fcs_fmd_index* fmd_handle(const fcs_fmd_index* h, const char* who) {
+  if (h) {
+    std::lock_guard<std::mutex> lk(g_fmd_mu);
+    auto it = g_fmd_live->find(h);
+    if (it != g_fmd_live->end() && !it->second->released) return it->second;
+  }
+  fail(FCS_ERR_INVALID, std::string("[E::") + who + "] " + (h ? "the index handle is not a live one" : "null index handle"));
+  return nullptr;
+}
+
+void fmd_drop_device(int device) {
+  std::lock_guard<std::mutex> lk(g_fmd_mu);
+  for (auto& [k, h] : *g_fmd_live)
+    if (h->device == device) h->released = true;
+}
+
+int fmd_params_check(const fcs_fmd_params* p, const char* who, int32_t& max_mems) {
+  if (!p) return fail(FCS_ERR_INVALID, std::string("[E::") + who + "] null params");
+  if (p->max_mems < 1)
+    return fail(FCS_ERR_INVALID, std::string("[E::") + who + "] max_mems " + std::to_string(p->max_mems) + " < 1");
+  if (p->min_len < 0 || p->max_mem_intv < 0)
+    return fail(FCS_ERR_INVALID, std::string("[E::") + who + "] negative min_len or max_mem_intv");
+  max_mems = p->max_mems;
+  return FCS_OK;
+}
+
+FmdCollectParams fmd_params(const fcs_fmd_params* p) {
+  return FmdCollectParams{p->min_len, p->split_len, p->split_width, p->max_mem_intv};
+}
+
+static_assert(sizeof(fcs_fmd_mem) == sizeof(FmdIv) && sizeof(FmdIv) == 32, "fcs_fmd_mem is the kernels' interval");
+
+}  // namespace
+
+extern "C" {
+
+int fcs_fmd_index_create(int32_t device, const uint64_t* occ, int64_t n_occ_words, const int64_t* C, int64_t n_rows,
+                         const uint64_t* sa, int64_t n_sa, int32_t sa_intv, const int64_t* special_rows,
+                         const int64_t* special_sa, int64_t n_special, int64_t flen, fcs_fmd_index** handle) {
+  if (!handle) return fail(FCS_ERR_INVALID, "[E::fcs_fmd_index_create] null handle pointer");
+  *handle = nullptr;
+  if (!occ || !C || n_rows < 1 || flen < 0 || sa_intv < 1 || n_sa < 0 || n_special < 0 ||
+      (n_special > 0 && (!special_rows || !special_sa)))
+    return fail(FCS_ERR_INVALID, "[E::fcs_fmd_index_create] bad arguments");
+  // the layout FmdIndex builds: a line per 64 rows and one of totals; a sample per sa_intv rows
+  if (n_occ_words != 8 * ((n_rows + 63) / 64 + 1))
+    return fail(FCS_ERR_INVALID, "[E::fcs_fmd_index_create] n_occ_words " + std::to_string(n_occ_words) +
+                                     " is not 8 * ((n_rows + 63) / 64 + 1)");
+  if (sa ? n_sa != (n_rows + sa_intv - 1) / sa_intv : (sa_intv != 1 || n_sa != 0))
+    return fail(FCS_ERR_INVALID, "[E::fcs_fmd_index_create] n_sa " + std::to_string(n_sa) + " does not fit n_rows and sa_intv" +
+                                     (sa ? "" : " (the suffix array may be left out with sa_intv 1 only)"));
+  for (int c = 0; c < 5; ++c)
+    if (C[c] < 0 || C[c + 1] < C[c] || C[c + 1] > n_rows)
+      return fail(FCS_ERR_INVALID, "[E::fcs_fmd_index_create] C is not a non-decreasing sequence within [0, n_rows]");
+  for (int64_t i = 0; i < n_special; ++i)
+    if (special_rows[i] < 0 || special_rows[i] >= n_rows || (i > 0 && special_rows[i] <= special_rows[i - 1]))
+      return fail(FCS_ERR_INVALID, "[E::fcs_fmd_index_create] special_rows is not sorted within [0, n_rows)");
+  int rc = check_device(device);
+  if (rc) return rc;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(FCS_ERR_DEVICE, "[E::fcs_fmd_index_create] device " + std::to_string(device) + " is not a gfx950");
+  FCS_SET_DEVICE((device));
+  auto h = std::make_unique<fcs_fmd_index>();
+  h->device = device;
+  std::vector<int64_t> pairs(2 * (size_t)n_special);
+  for (int64_t i = 0; i < n_special; ++i) pairs[2 * i] = special_rows[i], pairs[2 * i + 1] = special_sa[i];
+  const void* src[4] = {occ, C, sa, pairs.data()};
+  const size_t bytes[4] = {8 * (size_t)n_occ_words, 8 * 6, sa ? 8 * (size_t)n_sa : 0, 16 * (size_t)n_special};
+  for (int k = 0; k < 4 && !rc; ++k) {
+    if (!bytes[k]) continue;
+    // plain hipMalloc: the stream-ordered pool is not used in this library
+    if (hipMalloc(&h->mem[k], bytes[k]) != hipSuccess) {
+      h->mem[k] = nullptr;
+      rc = fail(FCS_ERR_NOMEM, "[E::fcs_fmd_index_create] hipMalloc of " + std::to_string(bytes[k]) + " bytes failed");
+    } else if (hipMemcpy(h->mem[k], src[k], bytes[k], hipMemcpyHostToDevice) != hipSuccess) {
+      rc = fail(FCS_ERR_DEVICE, "[E::fcs_fmd_index_create] the copy to the device failed");
+    }
+  }
+  if (rc) {
+    for (void* m : h->mem)
+      if (m) (void)hipFree(m);
+    return rc;
+  }
+  FmdDevIndex& dx = h->dx;
+  dx.occ = static_cast<const uint64_t*>(h->mem[0]);
+  dx.n_occ_words = n_occ_words;
+  dx.C = static_cast<const int64_t*>(h->mem[1]);
+  dx.n_rows = n_rows;
+  dx.sa = static_cast<const uint64_t*>(h->mem[2]);
+  dx.n_sa = n_sa;
+  dx.sa_intv = sa_intv;
+  dx.special = static_cast<const int64_t*>(h->mem[3]);
+  dx.n_special = n_special;
+  dx.flen = flen;
+  fcs_fmd_index* raw = h.release();
+  {
+    std::lock_guard<std::mutex> lk(g_fmd_mu);
+    (*g_fmd_live)[raw] = raw;
+  }
+  *handle = raw;
+  return FCS_OK;
+}
+
+int fcs_fmd_index_destroy(fcs_fmd_index* handle) {
+  if (!handle) return FCS_OK;
+  {
+    std::lock_guard<std::mutex> lk(g_fmd_mu);
+    auto it = g_fmd_live->find(handle);
+    if (it == g_fmd_live->end())
+      return fail(FCS_ERR_INVALID, "[E::fcs_fmd_index_destroy] the index handle is not a live one");
+    g_fmd_live->erase(it);
+  }
+  std::unique_ptr<fcs_fmd_index> h(handle);
+  if (h->released) return FCS_OK;  // its memory went with the device reset
+  FCS_SET_DEVICE((h->device));
+  for (void* m : h->mem)
+    if (m) FCS_HIP_CHECK(hipFree(m));
+  return FCS_OK;
+}
+
+int64_t fcs_fmd_collect_arena_bytes(int32_t n_reads, int32_t max_q_len) {
+  if (n_reads < 0 || max_q_len < 0) return fail(FCS_ERR_INVALID, "[E::fcs_fmd_collect_arena_bytes] bad arguments");
+  return fmd_collect_units(n_reads) * 2 * ((int64_t)max_q_len + 1) * (int64_t)sizeof(FmdIv);
+}
+
+int fcs_fmd_collect(const fcs_fmd_index* index, const uint8_t* codes, int64_t n_code_bytes, const int64_t* q_off,
+                    const int32_t* q_len, int32_t n_reads, const fcs_fmd_params* params, fcs_fmd_mem* mems,
+                    int32_t* n_mems, int32_t* overflow) {
+  if (n_reads < 0 || n_code_bytes < 0 || (n_code_bytes > 0 && !codes) ||
+      (n_reads > 0 && (!q_off || !q_len || !mems || !n_mems || !overflow)))
+    return fail(FCS_ERR_INVALID, "[E::fcs_fmd_collect] bad arguments");
+  int32_t max_mems = 0;
+  int rc = fmd_params_check(params, "fcs_fmd_collect", max_mems);
+  if (rc) return rc;
+  int32_t max_len = 0;
+  for (int32_t r = 0; r < n_reads; ++r) {
+    if (q_len[r] < 0)
+      return fail(FCS_ERR_INVALID, "[E::fcs_fmd_collect] read " + std::to_string(r) + " has negative length " +
+                                       std::to_string(q_len[r]));
+    if (q_off[r] < 0 || q_off[r] > n_code_bytes - q_len[r])
+      return fail(FCS_ERR_INVALID, "[E::fcs_fmd_collect] read " + std::to_string(r) + " at offset " +
+                                       std::to_string(q_off[r]) + " leaves the " + std::to_string(n_code_bytes) +
+                                       " code bytes");
+    max_len = std::max(max_len, q_len[r]);
+  }
+  const fcs_fmd_index* h = fmd_handle(index, "fcs_fmd_collect");
+  if (!h) return FCS_ERR_INVALID;
+  if (n_reads == 0) return FCS_OK;
+  if ((rc = check_device(h->device))) return rc;
+  FCS_SET_DEVICE((h->device));
+  const size_t n = (size_t)n_reads;
+  // one H2D copy (codes, offsets, lengths, order), one D2H copy (counts, flags, SMEMs)
+  Layout L;
+  const size_t ocodes = L.add((size_t)n_code_bytes), ooff = L.add(8 * n), olen = L.add(4 * n), oord = L.add(4 * n);
+  const size_t in_bytes = L.total;
+  const size_t onm = L.add(4 * n), oovf = L.add(4 * n), omems = L.add(n * (size_t)max_mems * sizeof(FmdIv));
+  const size_t host_bytes = L.total;
+  const size_t oarena = L.add((size_t)fcs_fmd_collect_arena_bytes(n_reads, max_len));
+  SessionLease lease;
+  if ((rc = lease.acquire(h->device))) return rc;
+  Session* S = lease.get();
+  if ((rc = S->ensure_host(host_bytes)) || (rc = S->ensure_dev(L.total))) return rc;
+  if (n_code_bytes) std::memcpy(S->h<void>(ocodes), codes, (size_t)n_code_bytes);
+  std::memcpy(S->h<void>(ooff), q_off, 8 * n);
+  std::memcpy(S->h<void>(olen), q_len, 4 * n);
+  {  // longest first (counting sort by length): the grid's last quads do not end on the long reads
+    std::vector<int32_t> start((size_t)max_len + 2, 0);
+    for (size_t r = 0; r < n; ++r) ++start[(size_t)(max_len - q_len[r]) + 1];
+    for (size_t k = 1; k < start.size(); ++k) start[k] += start[k - 1];
+    int32_t* ord = S->h<int32_t>(oord);
+    for (size_t r = 0; r < n; ++r) ord[start[(size_t)(max_len - q_len[r])]++] = (int32_t)r;
+  }
+  hipStream_t s = S->s;
+  const StreamDrain drain{s};
+  FCS_HIP_CHECK(hipMemcpyAsync(S->d<void>(0), S->h<void>(0), in_bytes, hipMemcpyHostToDevice, s));
+  if ((rc = launch_fmd_collect(h->dx, S->d<uint8_t>(ocodes), n_code_bytes, S->d<int64_t>(ooff), S->d<int32_t>(olen),
+                               S->d<int32_t>(oord), n_reads, fmd_params(params), S->d<FmdIv>(oarena), max_len + 1,
+                               S->d<FmdIv>(omems), max_mems, S->d<int32_t>(onm), S->d<int32_t>(oovf), s)))
+    return rc;
+  FCS_HIP_CHECK(hipMemcpyAsync(S->h<void>(onm), S->d<void>(onm), host_bytes - onm, hipMemcpyDeviceToHost, s));
+  FCS_HIP_CHECK(hipStreamSynchronize(s));
+  std::memcpy(n_mems, S->h<void>(onm), 4 * n);
+  std::memcpy(overflow, S->h<void>(oovf), 4 * n);
+  const FmdIv* hm = S->h<FmdIv>(omems);
+  for (size_t r = 0; r < n; ++r) {  // only the slots a read filled, in bwa's final order
+    const int32_t k = n_mems[r];
+    if (k < 0 || k > max_mems) return fail(FCS_ERR_DEVICE, "[E::fcs_fmd_collect] read " + std::to_string(r) + " came back with " + std::to_string(k) + " SMEMs");
+    fcs_fmd_mem* dst = mems + r * (size_t)max_mems;
+    std::memcpy(dst, hm + r * (size_t)max_mems, (size_t)k * sizeof(FmdIv));
+    std::stable_sort(dst, dst + k, [](const fcs_fmd_mem& a, const fcs_fmd_mem& b) { return a.qb != b.qb ? a.qb < b.qb : a.qe < b.qe; });
+  }
+  return FCS_OK;
+}
+
+int fcs_fmd_collect_dev(const fcs_fmd_index* index, const uint8_t* dev_codes, int64_t n_code_bytes,
+                        const int64_t* dev_q_off, const int32_t* dev_q_len, const int32_t* dev_order, int32_t n_reads,
+                        int32_t max_q_len, const fcs_fmd_params* params, void* dev_arena, int64_t arena_bytes,
+                        fcs_fmd_mem* dev_mems, int32_t* dev_n_mems, int32_t* dev_overflow, void* stream) {
+  if (n_reads < 0 || n_code_bytes < 0 || max_q_len < 0 || (n_code_bytes > 0 && !dev_codes) ||
+      (n_reads > 0 && (!dev_q_off || !dev_q_len || !dev_mems || !dev_n_mems || !dev_overflow || !dev_arena)))
+    return fail(FCS_ERR_INVALID, "[E::fcs_fmd_collect_dev] bad arguments");
+  int32_t max_mems = 0;
+  int rc = fmd_params_check(params, "fcs_fmd_collect_dev", max_mems);
+  if (rc) return rc;
+  if (n_reads > 0 && arena_bytes < fcs_fmd_collect_arena_bytes(n_reads, max_q_len))
+    return fail(FCS_ERR_INVALID, "[E::fcs_fmd_collect_dev] the arena holds " + std::to_string(arena_bytes) +
+                                     " bytes, the call needs " +
+                                     std::to_string(fcs_fmd_collect_arena_bytes(n_reads, max_q_len)));
+  const fcs_fmd_index* h = fmd_handle(index, "fcs_fmd_collect_dev");
+  if (!h) return FCS_ERR_INVALID;
+  if (n_reads == 0) return FCS_OK;
+  if ((rc = check_device(h->device))) return rc;
+  FCS_SET_DEVICE((h->device));
+  return launch_fmd_collect(h->dx, dev_codes, n_code_bytes, dev_q_off, dev_q_len, dev_order, n_reads, fmd_params(params),
+                            static_cast<FmdIv*>(dev_arena), max_q_len + 1, reinterpret_cast<FmdIv*>(dev_mems), max_mems,
+                            dev_n_mems, dev_overflow, static_cast<hipStream_t>(stream));
+}
+
+namespace {
+int fmd_locate_check(const fcs_fmd_index* index, const void* rows, int64_t n, int32_t& max_steps, const void* pos,
+                     const void* status, const char* who, const fcs_fmd_index*& h) {
+  if (n < 0 || max_steps < 0 || (n > 0 && (!rows || !pos || !status)))
+    return fail(FCS_ERR_INVALID, std::string("[E::") + who + "] bad arguments");
+  if (!(h = fmd_handle(index, who))) return FCS_ERR_INVALID;
+  if (!h->dx.sa)
+    return fail(FCS_ERR_INVALID, std::string("[E::") + who + "] the index was made without its suffix array (sa_intv 1)");
+  if (!max_steps) max_steps = (int32_t)std::min<int64_t>(32 * (int64_t)h->dx.sa_intv, INT32_MAX);
+  return FCS_OK;
+}
+}  // namespace
+
+int fcs_fmd_locate(const fcs_fmd_index* index, const int64_t* rows, int64_t n, int32_t max_steps, int64_t* pos,
+                   int32_t* status) {
+  const fcs_fmd_index* h = nullptr;
+  int rc = fmd_locate_check(index, rows, n, max_steps, pos, status, "fcs_fmd_locate", h);
+  if (rc || n == 0) return rc;
+  if ((rc = check_device(h->device))) return rc;
+  FCS_SET_DEVICE((h->device));
+  const size_t m = (size_t)n;
+  Layout L;
+  const size_t orows = L.add(8 * m), opos = L.add(8 * m), ost = L.add(4 * m);
+  SessionLease lease;
+  if ((rc = lease.acquire(h->device))) return rc;
+  Session* S = lease.get();
+  if ((rc = S->ensure_host(L.total)) || (rc = S->ensure_dev(L.total))) return rc;
+  std::memcpy(S->h<void>(orows), rows, 8 * m);
+  hipStream_t s = S->s;
+  const StreamDrain drain{s};
+  FCS_HIP_CHECK(hipMemcpyAsync(S->d<void>(orows), S->h<void>(orows), 8 * m, hipMemcpyHostToDevice, s));
+  if ((rc = launch_fmd_locate(h->dx, S->d<int64_t>(orows), n, max_steps, S->d<int64_t>(opos), S->d<int32_t>(ost), s)))
+    return rc;
+  FCS_HIP_CHECK(hipMemcpyAsync(S->h<void>(opos), S->d<void>(opos), L.total - opos, hipMemcpyDeviceToHost, s));
+  FCS_HIP_CHECK(hipStreamSynchronize(s));
+  std::memcpy(pos, S->h<void>(opos), 8 * m);
+  std::memcpy(status, S->h<void>(ost), 4 * m);
+  return FCS_OK;
+}
+
+int fcs_fmd_locate_dev(const fcs_fmd_index* index, const int64_t* dev_rows, int64_t n, int32_t max_steps,
+                       int64_t* dev_pos, int32_t* dev_status, void* stream) {
+  const fcs_fmd_index* h = nullptr;
+  int rc = fmd_locate_check(index, dev_rows, n, max_steps, dev_pos, dev_status, "fcs_fmd_locate_dev", h);
+  if (rc || n == 0) return rc;
+  if ((rc = check_device(h->device))) return rc;
+  FCS_SET_DEVICE((h->device));
+  return launch_fmd_locate(h->dx, dev_rows, n, max_steps, dev_pos, dev_status, static_cast<hipStream_t>(stream));
+}
+
 int fcs_bgzf_warmup(int32_t device, int32_t sessions, int64_t arena_bytes) {
   if (sessions < 0 || arena_bytes < 0) return fail(FCS_ERR_INVALID, "[E::fcs_bgzf_warmup] bad arguments");
   int rc = check_device(device);
@@ -2033,6 +2322,7 @@ int fcs_device_release(int32_t device) {
     for (auto it = g_stream_ws->begin(); it != g_stream_ws->end();)
       it = it->first.first == device ? g_stream_ws->erase(it) : std::next(it);
   }
+  fmd_drop_device(device);  // FMD-index handles of this device lose their memory below
   {
     std::lock_guard<std::mutex> lk(g_dev_mu);
     auto it = g_tables.find(device);
@@ -2047,6 +2337,6 @@ int fcs_device_release(int32_t device) {
   return FCS_OK;
 }
 
-int fcs_abi_symbol_count(void) { return 51; }
+int fcs_abi_symbol_count(void) { return 58; }
 
 }  // extern "C"

@@ -268,4 +268,35 @@ int launch_bgzf_deflate(const uint8_t* data, int64_t n_bytes, int32_t block_byte
 int launch_bgzf_compact(const uint8_t* slots, const int32_t* clen, int32_t n, int64_t* coff, uint8_t* out,
                         hipStream_t s);
 
+// ------------------------------------------------------------ FMD-index seeding
+// Device copy of an FmdIndex's arrays (fcs_fmd_index_create), shared by every
+// call and read-only.
+struct FmdDevIndex {
+  const uint64_t* occ;
+  int64_t n_occ_words;
+  const int64_t* C;  // 6 entries, on the device
+  int64_t n_rows;
+  const uint64_t* sa;
+  int64_t n_sa;
+  int32_t sa_intv;
+  const int64_t* special;  // (row, SA) pairs sorted by row
+  int64_t n_special;
+  int64_t flen;
+};
+struct FmdIv;             // fmd_smem.h: {k, l, s, qb, qe}, 32 bytes (fcs_fmd_mem's layout)
+struct FmdCollectParams;  // fmd_smem.h
+// One read per quad over a bounded grid (fmd_seed.hip).  arena: 2 * cap
+// intervals for each of fmd_collect_units(n_reads) quads, cap > the longest
+// read; order (nullable): the reads in launch order; out: max_mems slots per
+// read, n_mems / overflow one word per read.
+int64_t fmd_collect_units(int32_t n_reads);
+int launch_fmd_collect(const FmdDevIndex& dx, const uint8_t* codes, int64_t n_code_bytes, const int64_t* q_off,
+                       const int32_t* q_len, const int32_t* order, int32_t n_reads, const FmdCollectParams& P,
+                       FmdIv* arena, int32_t cap, FmdIv* out, int32_t max_mems, int32_t* n_mems, int32_t* overflow,
+                       hipStream_t s);
+// One lane per row: pos[i] = SA[rows[i]] and status[i] = 0, or status[i] != 0
+// (the step cap, or a row the index does not hold).
+int launch_fmd_locate(const FmdDevIndex& dx, const int64_t* rows, int64_t n, int32_t max_steps, int64_t* pos,
+                      int32_t* status, hipStream_t s);
+
 }  // namespace fcs

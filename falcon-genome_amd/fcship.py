@@ -190,6 +190,19 @@ _sig("fcs_bgzf_deflate_try", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int
                                        C.c_void_p, i32p, C.c_int32])
 _sig("fcs_bgzf_deflate_dev", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_void_p])
+_sig("fcs_fmd_index_create", C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                       C.POINTER(C.c_void_p)])
+_sig("fcs_fmd_index_destroy", C.c_int, [C.c_void_p])
+_sig("fcs_fmd_collect", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p])
+_sig("fcs_fmd_collect_arena_bytes", C.c_int64, [C.c_int32, C.c_int32])
+_sig("fcs_fmd_collect_dev", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p])
+_sig("fcs_fmd_locate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p])
+_sig("fcs_fmd_locate_dev", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p])
 _sig("fcs_synth_phmm_sizes", C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, i64p, i64p])
 _sig("fcs_synth_phmm", C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 10)
 _sig("fcs_synth_bsw_sizes", C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
@@ -610,3 +623,55 @@ def bgzf_deflate(data, block_bytes: int = FCS_BGZF_BLOCK_MAX, eof: bool = False,
     check(lib.fcs_bgzf_deflate(_ptr(d), len(d), block_bytes, int(eof), out.ctypes.data, cap, C.byref(got),
                                coff.ctypes.data, C.byref(n), device))
     return out[:got.value].tobytes(), coff[:n.value + 1].copy()
+
+
+# ------------------------------------------------------- FMD-index seeding
+FCS_FMD_MAX_MEMS_DEFAULT = 128
+FCS_FMD_LOCATED, FCS_FMD_STEP_CAP, FCS_FMD_BAD_ROW = 0, 1, 2
+FMD_MEM = np.dtype([("k", np.int64), ("l", np.int64), ("s", np.int64), ("qb", np.int32), ("qe", np.int32)])
+
+
+class FmdParams(C.Structure):
+    _fields_ = [("min_len", C.c_int32), ("split_len", C.c_int32), ("split_width", C.c_int32),
+                ("max_mems", C.c_int32), ("max_mem_intv", C.c_int64)]
+
+
+def fmd_index_create(occ, Carr, n_rows, sa, sa_intv, special_rows, special_sa, flen, device: int = 0):
+    """fcs_fmd_index_create over host arrays (sa may be None with sa_intv 1); the handle."""
+    occ = np.ascontiguousarray(occ, np.uint64)
+    Carr = np.ascontiguousarray(Carr, np.int64)
+    sa = None if sa is None else np.ascontiguousarray(sa, np.uint64)
+    rows = np.ascontiguousarray(special_rows, np.int64)
+    ssa = np.ascontiguousarray(special_sa, np.int64)
+    h = C.c_void_p()
+    check(lib.fcs_fmd_index_create(device, occ.ctypes.data, len(occ), Carr.ctypes.data, n_rows,
+                                   None if sa is None else sa.ctypes.data, 0 if sa is None else len(sa), sa_intv,
+                                   rows.ctypes.data, ssa.ctypes.data, len(rows), flen, C.byref(h)))
+    return h
+
+
+def fmd_index_destroy(handle) -> None:
+    check(lib.fcs_fmd_index_destroy(handle))
+
+
+def fmd_collect(handle, codes, q_off, q_len, min_len=19, split_len=28, split_width=10, max_mem_intv=20,
+                max_mems=FCS_FMD_MAX_MEMS_DEFAULT):
+    """fcs_fmd_collect: (mems[n_reads, max_mems] of FMD_MEM, n_mems, overflow)."""
+    codes = np.ascontiguousarray(codes, np.uint8)
+    q_off = np.ascontiguousarray(q_off, np.int64)
+    q_len = np.ascontiguousarray(q_len, np.int32)
+    n = len(q_len)
+    mems = np.zeros((n, max(max_mems, 1)), FMD_MEM)
+    n_mems, overflow = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    P = FmdParams(min_len, split_len, split_width, max_mems, max_mem_intv)
+    check(lib.fcs_fmd_collect(handle, codes.ctypes.data, len(codes), q_off.ctypes.data, q_len.ctypes.data, n,
+                              C.addressof(P), mems.ctypes.data, n_mems.ctypes.data, overflow.ctypes.data))
+    return mems, n_mems, overflow
+
+
+def fmd_locate(handle, rows, max_steps: int = 0):
+    """fcs_fmd_locate: (pos, status) of the BWT rows."""
+    rows = np.ascontiguousarray(rows, np.int64)
+    pos, status = np.zeros(len(rows), np.int64), np.zeros(len(rows), np.int32)
+    check(lib.fcs_fmd_locate(handle, rows.ctypes.data, len(rows), max_steps, pos.ctypes.data, status.ctypes.data))
+    return pos, status

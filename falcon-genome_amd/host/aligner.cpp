@@ -144,6 +144,18 @@ int approx_mapq_se(const Cand& c, int min_seed_len, int match, int mismatch) {
   return (int)(mapq * (1. - c.frac_rep) + .499);
 }
 
+// The collect parameters of seed_read (bwa -r 1.5, -y 20).
+SeedParams seed_params(const AlignOptions& opt) {
+  SeedParams P;
+  P.min_len = opt.k;
+  P.split_len = (int)(opt.k * 1.5 + .499);
+  P.split_width = 10;
+  P.max_mem_intv = 20;
+  P.max_occ = opt.max_occ;
+  P.max_mems = opt.seed_max_mems;
+  return P;
+}
+
 // Seeds and chains of one read (bwa mem_collect_intv + mem_chain +
 // mem_chain_flt): SMEMs of length >= min_seed_len on the FMD-index (both
 // strands at once), re-seeds inside long, rare SMEMs and the third-round
@@ -154,11 +166,14 @@ int approx_mapq_se(const Cand& c, int min_seed_len, int match, int mismatch) {
 // a chain that overlaps a kept heavier one on the query by >= mask_level of
 // the shorter and weighs < drop_ratio of it (and 2 min_seed_len less) is
 // dropped (the first such shadowed chain is kept for MAPQ, as bwa does).
-void seed_read(const KmerIndex& idx, const AlignOptions& opt, ReadAln& R) {
-  const std::vector<uint8_t>& q = R.code[0];
-  const int L = (int)q.size();
-  std::vector<BiInterval> mems;
-  idx.fmd().collect(q.data(), L, opt.k, (int)(opt.k * 1.5 + .499), 10, 20, mems);  // bwa -r 1.5, -y 20
+//
+// chain_read is everything after the SMEM list: frac_rep, the seeds of the sampled
+// occurrences, chains and their filter.  pos: SA[m.k + j] of those occurrences
+// in the loop's order (the device path, host/gpu_seed.h), or null: located on
+// the host index.
+void chain_read(const KmerIndex& idx, const AlignOptions& opt, ReadAln& R, const std::vector<BiInterval>& mems,
+                const int64_t* pos) {
+  const int L = (int)R.code[0].size();
   {  // bwa mem_chain's frac_rep: the union of the query spans of SMEMs with > max_occ hits
     std::vector<std::pair<int, int>> rep;
     for (const BiInterval& m : mems)
@@ -177,7 +192,8 @@ void seed_read(const KmerIndex& idx, const AlignOptions& opt, ReadAln& R) {
     const int64_t step = m.s > opt.max_occ ? m.s / opt.max_occ : 1;
     for (int64_t j = 0, kept = 0; j < m.s && kept < opt.max_occ; j += step, ++kept) {
       Seed sd;
-      idx.fmd().locate(m, j, sd.contig, sd.rbeg, sd.rev);
+      if (pos) idx.text_map().locate(*pos++, m.qe - m.qb, sd.contig, sd.rbeg, sd.rev);
+      else idx.fmd().locate(m, j, sd.contig, sd.rbeg, sd.rev);
       sd.len = m.qe - m.qb;
       sd.qbeg = sd.rev ? L - m.qe : m.qb;  // query offset in the oriented read
       seeds.push_back(sd);
@@ -265,6 +281,14 @@ void seed_read(const KmerIndex& idx, const AlignOptions& opt, ReadAln& R) {
     if (chains[j].first >= 0) chains[chains[j].first].kept = 1;
   for (Chain& ch : chains)
     if (ch.kept > 0) R.chains.push_back(std::move(ch));
+}
+
+void seed_read(const KmerIndex& idx, const AlignOptions& opt, ReadAln& R) {
+  const std::vector<uint8_t>& q = R.code[0];
+  const SeedParams P = seed_params(opt);
+  std::vector<BiInterval> mems;
+  idx.fmd().collect(q.data(), (int)q.size(), P.min_len, P.split_len, P.split_width, P.max_mem_intv, mems);
+  chain_read(idx, opt, R, mems, nullptr);
 }
 
 // mem_chain2aln's test: is seed s (almost) inside a region already made? (then
@@ -1178,8 +1202,25 @@ void align_batch(const KmerIndex& idx, const std::vector<std::string>& seqs, con
     R.seq[1] = revcomp(seqs[r]);
     R.code[0] = encode(R.seq[0]);
     R.code[1] = encode(R.seq[1]);
-    seed_read(idx, opt, R);
+    if (!opt.gpu_seed) seed_read(idx, opt, R);
   });
+  if (opt.gpu_seed && !reads.empty()) {  // one collect and one locate call for the chunk, then chaining per read
+    std::vector<const uint8_t*> q(reads.size());
+    std::vector<int> qlen(reads.size());
+    for (size_t r = 0; r < reads.size(); ++r) q[r] = reads[r].code[0].data(), qlen[r] = (int)reads[r].code[0].size();
+    SeedBatch sb;
+    gpu_seed_batch(idx.fmd(), idx.device_fmd(opt.gpu), q.data(), qlen.data(), reads.size(), seed_params(opt),
+                   opt.threads, sb);
+    const uint64_t tc = now_us();
+    parallel_for(reads.size(), opt.threads,
+                 [&](size_t r) { chain_read(idx, opt, reads[r], sb.mems[r], sb.pos[r].data()); });
+    st.seed_collect_seconds += sb.collect_seconds;
+    st.seed_locate_seconds += sb.locate_seconds;
+    st.seed_chain_seconds += (now_us() - tc) / 1e6;
+    st.seed_gpu_reads += (int64_t)reads.size();
+    st.seed_host_reads += sb.host_reads;
+    st.seed_host_rows += sb.host_rows;
+  }
   const uint64_t t1 = now_us();
   st.seed_seconds += (t1 - t0) / 1e6;
   extend_chains(idx, st.params, opt, reads, st);
@@ -1203,6 +1244,8 @@ KmerIndex::KmerIndex(const Reference& ref, int k, const std::string& index_path)
   if (!index_path.empty()) fmd_ = FmdIndex::load(index_path, codes_);
   loaded_ = fmd_ != nullptr;
   if (!fmd_) fmd_ = std::make_unique<FmdIndex>(codes_);
+  map_ = std::make_unique<TextMap>(codes_);
+  dev_ = std::make_unique<FmdDeviceCopies>(*fmd_);
 }
 
 std::string fmd_index_path(const std::string& fasta) { return fasta + ".fcsidx"; }
@@ -1471,6 +1514,12 @@ void add_stats(AlignStats& tot, const AlignStats& st) {
   tot.extend_seconds += st.extend_seconds;
   tot.pair_seconds += st.pair_seconds;
   tot.record_seconds += st.record_seconds;
+  tot.seed_collect_seconds += st.seed_collect_seconds;
+  tot.seed_locate_seconds += st.seed_locate_seconds;
+  tot.seed_chain_seconds += st.seed_chain_seconds;
+  tot.seed_gpu_reads += st.seed_gpu_reads;
+  tot.seed_host_reads += st.seed_host_reads;
+  tot.seed_host_rows += st.seed_host_rows;
   tot.ext_tasks += st.ext_tasks;
   tot.global_tasks += st.global_tasks;
   if (st.pe_pairs) tot.pe_pairs = st.pe_pairs, tot.pe_low = st.pe_low, tot.pe_high = st.pe_high,
@@ -1497,6 +1546,15 @@ AlignStats align_fastq(const AlignJob& job, const std::vector<int>& devices, std
   AlignOptions base;
   base.rg = job.rg;
   base.chunk_size = conf().get_int("bwa.chunk_size");
+  const bool want_gpu_seed = conf().get_bool("bwa.gpu_seed");
+  base.gpu_seed = want_gpu_seed && gpu_seed_available();
+  if (want_gpu_seed && !base.gpu_seed) {
+    static std::once_flag said;
+    std::call_once(said, [] {
+      std::fprintf(stderr, "[fcs-genome align] bwa.gpu_seed: the loaded libfcship has no fcs_fmd_* entry points; "
+                           "seeding runs on the host\n");
+    });
+  }
   const int nslot = (int)gpus.size();
   {
     // bwa.nt host threads for the whole job, shared by the device slots
@@ -1698,6 +1756,12 @@ AlignStats align_fastq(const AlignJob& job, const std::vector<int>& devices, std
       << idx.fmd().sa_intv() << "), FASTQ + alignment " << (t_aln - t_idx) / 1e6 << " s (alignment thread-seconds " << tot.seconds
       << ": seeding " << tot.seed_seconds << ", extension " << tot.extend_seconds << ", pairing " << tot.pair_seconds
       << ", records " << tot.record_seconds << "), sort + BAM + index " << (t_end - t_aln) / 1e6 << " s\n";
+  if (base.gpu_seed)
+    rep << "[fcs-genome align] GPU seeding (bwa.gpu_seed): " << tot.seed_gpu_reads << " reads through the device, "
+        << tot.seed_host_reads << " of them collected on the host (more than " << base.seed_max_mems
+        << " SMEMs), " << tot.seed_host_rows << " rows located on the host; seeding thread-seconds: collect "
+        << tot.seed_collect_seconds << ", locate " << tot.seed_locate_seconds << ", chain " << tot.seed_chain_seconds
+        << "\n";
   report = rep.str();
   return tot;
 }

@@ -44,6 +44,7 @@
 #include "fasta.h"
 #include "fmindex.h"
 #include "fcship.h"
+#include "gpu_seed.h"
 
 namespace fcsg {
 
@@ -61,6 +62,8 @@ struct AlignOptions {
   int min_out_score = 30;    // bwa -T: regions scoring below are not output
   int pen_unpaired = 17;     // bwa -U
   int max_matesw = 50;       // bwa max_matesw: rescue anchors per read
+  bool gpu_seed = false;     // bwa.gpu_seed: SMEM collection and SA lookups of a chunk on the GPU (host/gpu_seed.h)
+  int seed_max_mems = 32;    // device SMEM slots per read (1 KB); a read with more is collected on the host
   int64_t read_id0 = 0;      // index of the batch's first read (pair) in the input: bwa's hash seed for ties
   std::string rg = "sample", sample = "sample", platform = "illumina", library = "sample";
 };
@@ -73,6 +76,11 @@ struct AlignStats {
   // wall seconds of the phases: seeding + chaining, extension (host protocol +
   // GPU calls), pairing / primary choice, record building
   double seed_seconds = 0, extend_seconds = 0, pair_seconds = 0, record_seconds = 0;
+  // bwa.gpu_seed: seed_seconds split into the collect call (with the host's
+  // overflow reads), the locate call and chaining; reads seeded through the
+  // device, those of them collected on the host, rows located on the host
+  double seed_collect_seconds = 0, seed_locate_seconds = 0, seed_chain_seconds = 0;
+  int64_t seed_gpu_reads = 0, seed_host_reads = 0, seed_host_rows = 0;
   // paired: the insert-size estimate of the (last) batch
   int pe_pairs = 0, pe_low = 0, pe_high = 0;
   double pe_avg = 0, pe_std = 0;
@@ -91,6 +99,10 @@ class KmerIndex {
   // the contig's bases as codes 0..4 (A, C, G, T, other)
   const std::vector<uint8_t>& codes(int contig) const { return codes_[contig]; }
   const FmdIndex& fmd() const { return *fmd_; }
+  // bwa.gpu_seed: the index's copy on `device` (made on first use, one per
+  // device) and the conversion of the positions the device returns
+  fcs_fmd_index* device_fmd(int device) const { return dev_->get(device); }
+  const TextMap& text_map() const { return *map_; }
   // bwa's packed-reference coordinates: the contig's start in the
   // concatenated forward strand, and its total length l_pac (the reverse
   // strand occupies [l_pac, 2 l_pac))
@@ -104,6 +116,8 @@ class KmerIndex {
   std::vector<int64_t> off_;
   int64_t l_pac_ = 0;
   std::unique_ptr<FmdIndex> fmd_;
+  std::unique_ptr<TextMap> map_;
+  std::unique_ptr<FmdDeviceCopies> dev_;  // after fmd_: destroyed first
 };
 
 // The saved FMD-index of a FASTA (fcs-genome index): <fasta>.fcsidx.

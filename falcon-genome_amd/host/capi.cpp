@@ -17,6 +17,7 @@
 #include "fasta.h"
 #include "fmindex.h"
 #include "gatk_prep.h"
+#include "gpu_seed.h"
 #include "seedext.h"
 #include "aligner.h"
 #include "intervals.h"
@@ -166,6 +167,148 @@ int fcsg_fmd_smems(const uint8_t* ref, const int64_t* clen, int ncontig, const u
     n = (int)v.size();
   });
   return rc < 0 ? rc : n;
+}
+
+// The aligner's seeding of a batch of reads (codes 0..4, read r at q[qoff[r] ..
+// qoff[r] + qlen[r])) on an FMD-index of the given contigs, on the host index
+// (gpu 0: FmdIndex::collect / locate) or through the device entry points (gpu
+// 1: host/gpu_seed.h on device 0).  Per read r: n_mems[r] SMEMs {qb, qe, s, k,
+// l} at mems + 5 * mem_off[r] in collect's order, and n_loc[r] located
+// occurrences {contig, offset, reverse} at loc + 3 * loc_off[r], those
+// seed_read samples (at most max_occ per SMEM); mem_off / loc_off are the
+// prefix sums the call writes (n + 1 entries); a total beyond mem_cap /
+// loc_cap is an error.  *fallback = reads the device handed back to the host.
+// sa_intv / index_path as fcsg_fmd_smems.
+int fcsg_fmd_seed_batch(const uint8_t* ref, const int64_t* clen, int ncontig, const uint8_t* q, const int64_t* qoff,
+                        const int32_t* qlen, int n, int min_len, int split_len, int split_width, int max_mem_intv,
+                        int max_occ, int sa_intv, const char* index_path, int gpu, int max_mems, int64_t* mems,
+                        int64_t* mem_off, int32_t* n_mems, int64_t mem_cap, int64_t* loc, int64_t* loc_off,
+                        int32_t* n_loc, int64_t loc_cap, int64_t* fallback) {
+  return guard([&] {
+    std::vector<std::vector<uint8_t>> cs;
+    int64_t o = 0;
+    for (int i = 0; i < ncontig; ++i) {
+      cs.emplace_back(ref + o, ref + o + clen[i]);
+      o += clen[i];
+    }
+    std::unique_ptr<FmdIndex> built = std::make_unique<FmdIndex>(cs, sa_intv), mapped;
+    if (index_path && *index_path) {
+      built->save(index_path);
+      built.reset();
+      mapped = FmdIndex::load(index_path, cs);
+      if (!mapped) throw internalError("saved FMD-index did not load");
+    }
+    const FmdIndex& fmd = mapped ? *mapped : *built;
+    SeedParams P;
+    P.min_len = min_len, P.split_len = split_len, P.split_width = split_width, P.max_mem_intv = max_mem_intv;
+    P.max_occ = max_occ, P.max_mems = max_mems;
+    if (max_occ < 1) throw invalidParam("fcsg_fmd_seed_batch: max_occ");
+    SeedBatch sb;
+    if (gpu) {
+      if (!gpu_seed_available()) throw internalError("fcsg_fmd_seed_batch: libfcship has no fcs_fmd_* entry points");
+      FmdDeviceCopies dev(fmd);
+      std::vector<const uint8_t*> qp(n);
+      for (int r = 0; r < n; ++r) qp[r] = q + qoff[r];
+      gpu_seed_batch(fmd, dev.get(0), qp.data(), qlen, (size_t)n, P, 4, sb);
+    } else {
+      sb.mems.resize(n);
+      for (int r = 0; r < n; ++r)
+        fmd.collect(q + qoff[r], qlen[r], min_len, split_len, split_width, max_mem_intv, sb.mems[r]);
+    }
+    const TextMap map(cs);
+    int64_t nm = 0, nl = 0;
+    for (int r = 0; r < n; ++r) {
+      mem_off[r] = nm, loc_off[r] = nl;
+      const int64_t* pos = gpu ? sb.pos[r].data() : nullptr;
+      for (const BiInterval& m : sb.mems[r]) {
+        if (nm >= mem_cap) throw invalidParam("fcsg_fmd_seed_batch: SMEM capacity");
+        int64_t* w = mems + 5 * nm++;
+        w[0] = m.qb, w[1] = m.qe, w[2] = m.s, w[3] = m.k, w[4] = m.l;
+        const int64_t step = m.s > max_occ ? m.s / max_occ : 1;
+        for (int64_t j = 0, kept = 0; j < m.s && kept < max_occ; j += step, ++kept) {
+          if (nl >= loc_cap) throw invalidParam("fcsg_fmd_seed_batch: location capacity");
+          int c;
+          int64_t off;
+          bool rev;
+          if (gpu) map.locate(*pos++, m.qe - m.qb, c, off, rev);
+          else fmd.locate(m, j, c, off, rev);
+          int64_t* l = loc + 3 * nl++;
+          l[0] = c, l[1] = off, l[2] = rev;
+        }
+      }
+      n_mems[r] = (int32_t)(nm - mem_off[r]);
+      n_loc[r] = (int32_t)(nl - loc_off[r]);
+    }
+    mem_off[n] = nm, loc_off[n] = nl;
+    *fallback = sb.host_reads;
+  });
+}
+
+// Host seeding rates for tools/bench_seed.py: FmdIndex::collect of every read,
+// then FmdIndex::locate of the occurrences seed_read samples, each phase on
+// `threads` threads (parallel_for, as align_batch runs them) and timed alone.
+// out = {collect seconds, locate seconds}, counts = {SMEMs, rows located}.
+int fcsg_fmd_host_rates(const uint8_t* ref, const int64_t* clen, int ncontig, const uint8_t* q, const int64_t* qoff,
+                        const int32_t* qlen, int n, int min_len, int split_len, int split_width, int max_mem_intv,
+                        int max_occ, int sa_intv, int threads, double* out, int64_t* counts) {
+  return guard([&] {
+    std::vector<std::vector<uint8_t>> cs;
+    int64_t o = 0;
+    for (int i = 0; i < ncontig; ++i) {
+      cs.emplace_back(ref + o, ref + o + clen[i]);
+      o += clen[i];
+    }
+    const FmdIndex fmd(cs, sa_intv);
+    std::vector<std::vector<BiInterval>> mems(n);
+    const uint64_t t0 = now_us();
+    parallel_for((size_t)n, threads, [&](size_t r) {
+      fmd.collect(q + qoff[r], qlen[r], min_len, split_len, split_width, max_mem_intv, mems[r]);
+    });
+    const uint64_t t1 = now_us();
+    std::vector<int64_t> rows(n, 0);
+    parallel_for((size_t)n, threads, [&](size_t r) {
+      for (const BiInterval& m : mems[r]) {
+        const int64_t step = m.s > max_occ ? m.s / max_occ : 1;
+        for (int64_t j = 0, kept = 0; j < m.s && kept < max_occ; j += step, ++kept) {
+          int c;
+          int64_t off;
+          bool rev;
+          fmd.locate(m, j, c, off, rev);
+          ++rows[r];
+        }
+      }
+    });
+    out[0] = (t1 - t0) / 1e6;
+    out[1] = (now_us() - t1) / 1e6;
+    counts[0] = counts[1] = 0;
+    for (int r = 0; r < n; ++r) counts[0] += (int64_t)mems[r].size(), counts[1] += rows[r];
+  });
+}
+
+// The arrays of the FMD-index of the given contigs, as the fcs_fmd_* entry
+// points of libfcship take them (FmdIndex::view): sizes = {n_occ_words, n_rows,
+// n_sa, n_special, flen}; the arrays are filled when non-null (call once for
+// the sizes, then with buffers of those sizes; C6 holds 6 entries).
+int fcsg_fmd_index_arrays(const uint8_t* ref, const int64_t* clen, int ncontig, int sa_intv, int64_t* sizes,
+                          uint64_t* occ, int64_t* C6, uint64_t* sa, int64_t* special_rows, int64_t* special_sa) {
+  return guard([&] {
+    std::vector<std::vector<uint8_t>> cs;
+    int64_t o = 0;
+    for (int i = 0; i < ncontig; ++i) {
+      cs.emplace_back(ref + o, ref + o + clen[i]);
+      o += clen[i];
+    }
+    const FmdIndex fmd(cs, sa_intv);
+    const FmdView v = fmd.view();
+    sizes[0] = v.n_occ_words, sizes[1] = v.n_rows, sizes[2] = v.n_sa, sizes[3] = v.n_special, sizes[4] = v.flen;
+    if (occ) std::copy(v.occ, v.occ + v.n_occ_words, occ);
+    if (C6) std::copy(v.C, v.C + 6, C6);
+    if (sa) std::copy(v.sa, v.sa + v.n_sa, sa);
+    for (int64_t i = 0; i < v.n_special; ++i) {
+      if (special_rows) special_rows[i] = v.special[2 * i];
+      if (special_sa) special_sa[i] = v.special[2 * i + 1];
+    }
+  });
 }
 
 // bwa's seed-extension protocol (host/seedext.h) over n seeds on one reference

@@ -30,6 +30,21 @@ struct BiInterval {
   int qb = 0, qe = 0;  // query range [qb, qe) of the match
 };
 
+// The index arrays as FmdIndex holds them (read-only, valid while the index
+// lives): what a device copy of the index is made from.
+struct FmdView {
+  const uint64_t* occ;
+  int64_t n_occ_words;
+  const int64_t* C;  // 7 entries: C[c] = symbols < c, C[6] = n_rows
+  int64_t n_rows;
+  const uint64_t* sa;
+  int64_t n_sa;
+  int sa_intv;
+  const int64_t* special;  // n_special (row, SA) pairs
+  int64_t n_special;
+  int64_t flen;
+};
+
 class FmdIndex {
  public:
   // contigs as codes 0..4 (A, C, G, T, other).  sa_intv: keep SA[i] for rows
@@ -46,6 +61,9 @@ class FmdIndex {
   static std::unique_ptr<FmdIndex> load(const std::string& path, const std::vector<std::vector<uint8_t>>& contigs);
   int64_t size() const { return n_; }
   int sa_intv() const { return intv_; }
+  FmdView view() const {
+    return {occ_, nocc_, C_.data(), n_, sa_, nsa_, intv_, reinterpret_cast<const int64_t*>(special_), nspecial_, flen_};
+  }
   // bwt_smem1: SMEMs of q (codes 0..4) overlapping position x with at least
   // min_intv occurrences; returns the next start position (bwa's return value).
   int smem1(const uint8_t* q, int len, int x, int64_t min_intv, std::vector<BiInterval>& out) const;

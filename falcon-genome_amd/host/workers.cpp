@@ -324,6 +324,7 @@ GpuReleaseWorker::GpuReleaseWorker(std::vector<int> gpus, BackgroundExecutor* wa
 
 int GpuReleaseWorker::run(TaskContext&) {
   if (warm_) warm_->wait();
+  release_fmd_device_copies();  // FMD-index copies (bwa.gpu_seed) go before their device is reset
   // a failure only means the teardown happens at exit as before
   for (int d : gpus_)
     if (d >= 0 && fcs_device_release(d) != FCS_OK) std::fprintf(stderr, "[W::fcs-genome] %s\n", fcs_last_error());

@@ -424,6 +424,80 @@ int fcs_bgzf_deflate_try(const uint8_t* data, int64_t n_bytes, int32_t block_byt
 int fcs_bgzf_deflate_dev(const uint8_t* dev_data, int64_t n_bytes, int32_t block_bytes, uint8_t* dev_slots,
                          int32_t* dev_clen, int32_t device, void* stream);
 
+/* ------------------------------------------------- FMD-index seeding (§8 f4) */
+/* The aligner's seeding (bwa bwt_smem1 / mem_collect_intv and bwt_sa) on the
+ * GPU: the SMEMs of a batch of reads on an FMD-index held on the device, and
+ * suffix-array lookups of BWT rows by LF walks.  Every integer returned is the
+ * one the host index (fcs-genome's FmdIndex::collect / locate) computes.
+ *
+ * fcs_fmd_index_create copies the index arrays to `device` once: occ (one
+ * 64-byte line per 64 BWT positions: the counts of A, C, G, T before the
+ * block, then their bit vectors in it; one extra line of totals), C[0..5]
+ * (symbols smaller than c), the suffix array sampled every sa_intv rows (sa
+ * may be null with sa_intv 1: such an index collects, and its owner reads
+ * SA[row] itself), and the rows with no LF step as n_special (row, SA) pairs
+ * sorted by row.  flen is the length of the forward text.  The handle is
+ * read-only and may be used by any number of threads at once;
+ * fcs_fmd_index_destroy frees it (not while a call is using it, and before
+ * fcs_device_release of its device; a handle that outlives the release only
+ * fails, FCS_ERR_INVALID).
+ *
+ * fcs_fmd_collect: host buffers, synchronous.  Read r is codes[q_off[r] ..
+ * q_off[r] + q_len[r]) (0..3 = A, C, G, T; anything else is N).  Its SMEMs go
+ * to mems[r * max_mems ...] in (qb, qe) order, n_mems[r] of them; a read with
+ * more than max_mems SMEMs gets overflow[r] = 1 and n_mems[r] = 0, and its
+ * caller collects it on the host (no read is dropped for the depth of the
+ * interval stacks, which are sized for the longest read of the call).
+ * params->max_mems is at least 1; FCS_FMD_MAX_MEMS_DEFAULT is 128 slots of 32
+ * bytes, above the 114 SMEMs of the densest read of the test batches (251
+ * bases, min_len 1; with bwa's parameters no read of those batches has more
+ * than 14: tools/micro/fmd_smem_test.cpp prints the counts).
+ *
+ * fcs_fmd_collect_dev: device buffers, stream-ordered, no sync; SMEMs in
+ * emission order (rounds 1, 2, 3: the caller applies the stable sort by
+ * (qb, qe)).  dev_order (nullable) is the order in which the reads are
+ * taken, longest first for balance; max_q_len bounds every q_len (a longer
+ * read is flagged as overflow); dev_arena holds
+ * fcs_fmd_collect_arena_bytes(n_reads, max_q_len) bytes of scratch.
+ *
+ * fcs_fmd_locate / fcs_fmd_locate_dev: pos[i] = SA[rows[i]] with status[i] =
+ * FCS_FMD_LOCATED, by at most max_steps LF steps to a sampled or special row
+ * (0: 32 * sa_intv; a walk ends at each step with probability 1 / sa_intv,
+ * so about e^-32 of the rows run into that cap); FCS_FMD_STEP_CAP rows, and
+ * FCS_FMD_BAD_ROW ones (outside the index), are left to the caller. */
+typedef struct fcs_fmd_index fcs_fmd_index;
+typedef struct {
+  int64_t k, l, s; /* SA interval [k, k + s) of the match, [l, l + s) of its reverse complement */
+  int32_t qb, qe;  /* query range [qb, qe) */
+} fcs_fmd_mem;
+typedef struct {
+  int32_t min_len;      /* bwa -k */
+  int32_t split_len;    /* re-seed SMEMs at least this long ... (bwa: (int)(min_len * 1.5 + .499)) */
+  int32_t split_width;  /* ... with at most this many occurrences (bwa: 10) */
+  int32_t max_mems;     /* output slots per read, >= 1 (FCS_FMD_MAX_MEMS_DEFAULT) */
+  int64_t max_mem_intv; /* third round below this many occurrences (bwa: 20); 0: no third round */
+} fcs_fmd_params;
+#define FCS_FMD_MAX_MEMS_DEFAULT 128
+#define FCS_FMD_LOCATED 0
+#define FCS_FMD_STEP_CAP 1
+#define FCS_FMD_BAD_ROW 2
+int fcs_fmd_index_create(int32_t device, const uint64_t* occ, int64_t n_occ_words, const int64_t* C, int64_t n_rows,
+                         const uint64_t* sa, int64_t n_sa, int32_t sa_intv, const int64_t* special_rows,
+                         const int64_t* special_sa, int64_t n_special, int64_t flen, fcs_fmd_index** handle);
+int fcs_fmd_index_destroy(fcs_fmd_index* handle);
+int fcs_fmd_collect(const fcs_fmd_index* index, const uint8_t* codes, int64_t n_code_bytes, const int64_t* q_off,
+                    const int32_t* q_len, int32_t n_reads, const fcs_fmd_params* params, fcs_fmd_mem* mems,
+                    int32_t* n_mems, int32_t* overflow);
+int64_t fcs_fmd_collect_arena_bytes(int32_t n_reads, int32_t max_q_len);
+int fcs_fmd_collect_dev(const fcs_fmd_index* index, const uint8_t* dev_codes, int64_t n_code_bytes,
+                        const int64_t* dev_q_off, const int32_t* dev_q_len, const int32_t* dev_order, int32_t n_reads,
+                        int32_t max_q_len, const fcs_fmd_params* params, void* dev_arena, int64_t arena_bytes,
+                        fcs_fmd_mem* dev_mems, int32_t* dev_n_mems, int32_t* dev_overflow, void* stream);
+int fcs_fmd_locate(const fcs_fmd_index* index, const int64_t* rows, int64_t n, int32_t max_steps, int64_t* pos,
+                   int32_t* status);
+int fcs_fmd_locate_dev(const fcs_fmd_index* index, const int64_t* dev_rows, int64_t n, int32_t max_steps,
+                       int64_t* dev_pos, int32_t* dev_status, void* stream);
+
 /* ---------------------------------------------- synthetic workload builders */
 /* Seeded generators for the benchmark configurations (BASELINE.json C2/C3).
  * Deterministic for a given seed.  Callers size the buffers with the *_sizes
