@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "fcship_internal.h"
+#include "fmd_expand.h"
 #include "fmd_smem.h"
 
 namespace fcs {
@@ -2270,6 +2271,184 @@ int fcs_fmd_locate_dev(const fcs_fmd_index* index, const int64_t* dev_rows, int6
   return launch_fmd_locate(h->dx, dev_rows, n, max_steps, dev_pos, dev_status, static_cast<hipStream_t>(stream));
 }
 
+namespace {
+// The device scratch of a fused seeding call, as fcship.h lists its parts.
+struct FmdSeedWs {
+  size_t arena, slots, place, n_mems, n_eff, n_rows, rows;
+};
+FmdSeedWs fmd_seed_ws(Layout& L, int32_t n_reads, int32_t max_q_len, int32_t max_mems, int64_t row_cap) {
+  const size_t n = (size_t)n_reads;
+  FmdSeedWs w;
+  w.arena = L.add((size_t)fcs_fmd_collect_arena_bytes(n_reads, max_q_len));
+  w.slots = L.add(n * (size_t)max_mems * sizeof(FmdIv));
+  w.place = L.add(n * (size_t)max_mems * sizeof(FmdSeedPlace));
+  w.n_mems = L.add(4 * n);
+  w.n_eff = L.add(4 * n);
+  w.n_rows = L.add(8 * n);
+  w.rows = L.add(8 * (size_t)row_cap);
+  return w;
+}
+
+// What fcs_fmd_seed and fcs_fmd_seed_dev check alike, before any device work.
+int fmd_seed_check(const fcs_fmd_seed_params* p, int64_t mem_cap, int64_t row_cap, const void* mems, const void* mem_off,
+                   const void* pos, const void* row_off, const void* overflow, int32_t n_reads, const char* who,
+                   int32_t& max_mems) {
+  if (!p) return fail(FCS_ERR_INVALID, std::string("[E::") + who + "] null params");
+  int rc = fmd_params_check(&p->collect, who, max_mems);
+  if (rc) return rc;
+  if (p->max_occ < 1)
+    return fail(FCS_ERR_INVALID, std::string("[E::") + who + "] max_occ " + std::to_string(p->max_occ) + " < 1");
+  if (p->max_steps < 0) return fail(FCS_ERR_INVALID, std::string("[E::") + who + "] negative max_steps");
+  if (mem_cap < 0 || row_cap < 0)
+    return fail(FCS_ERR_INVALID, std::string("[E::") + who + "] negative capacity (mem_cap " + std::to_string(mem_cap) +
+                                     ", row_cap " + std::to_string(row_cap) + ")");
+  if (!mem_off || !row_off || (n_reads > 0 && !overflow) || (mem_cap > 0 && !mems) || (row_cap > 0 && !pos))
+    return fail(FCS_ERR_INVALID, std::string("[E::") + who + "] null output");
+  return FCS_OK;
+}
+
+int32_t fmd_seed_steps(const fcs_fmd_index* h, int32_t max_steps) {
+  return max_steps ? max_steps : (int32_t)std::min<int64_t>(32 * (int64_t)h->dx.sa_intv, INT32_MAX);
+}
+}  // namespace
+
+int64_t fcs_fmd_seed_workspace_bytes(int32_t n_reads, int32_t max_q_len, int32_t max_mems, int64_t row_cap) {
+  if (n_reads < 0 || max_q_len < 0 || max_mems < 1 || row_cap < 0)
+    return fail(FCS_ERR_INVALID, "[E::fcs_fmd_seed_workspace_bytes] bad arguments");
+  Layout L;
+  (void)fmd_seed_ws(L, n_reads, max_q_len, max_mems, row_cap);
+  return (int64_t)L.total;
+}
+
+int fcs_fmd_seed(const fcs_fmd_index* index, const uint8_t* codes, int64_t n_code_bytes, const int64_t* q_off,
+                 const int32_t* q_len, int32_t n_reads, const fcs_fmd_seed_params* params, fcs_fmd_mem* mems,
+                 int64_t mem_cap, int64_t* mem_off, int64_t* pos, int64_t row_cap, int64_t* row_off,
+                 int32_t* overflow) {
+  if (n_reads < 0 || n_code_bytes < 0 || (n_code_bytes > 0 && !codes) || (n_reads > 0 && (!q_off || !q_len)))
+    return fail(FCS_ERR_INVALID, "[E::fcs_fmd_seed] bad arguments");
+  int32_t max_mems = 0;
+  int rc = fmd_seed_check(params, mem_cap, row_cap, mems, mem_off, pos, row_off, overflow, n_reads, "fcs_fmd_seed",
+                          max_mems);
+  if (rc) return rc;
+  int32_t max_len = 0;
+  for (int32_t r = 0; r < n_reads; ++r) {
+    if (q_len[r] < 0)
+      return fail(FCS_ERR_INVALID, "[E::fcs_fmd_seed] read " + std::to_string(r) + " has negative length " +
+                                       std::to_string(q_len[r]));
+    if (q_off[r] < 0 || q_off[r] > n_code_bytes - q_len[r])
+      return fail(FCS_ERR_INVALID, "[E::fcs_fmd_seed] read " + std::to_string(r) + " at offset " +
+                                       std::to_string(q_off[r]) + " leaves the " + std::to_string(n_code_bytes) +
+                                       " code bytes");
+    max_len = std::max(max_len, q_len[r]);
+  }
+  const fcs_fmd_index* h = fmd_handle(index, "fcs_fmd_seed");
+  if (!h) return FCS_ERR_INVALID;
+  if (n_reads == 0) {
+    mem_off[0] = row_off[0] = 0;
+    return FCS_OK;
+  }
+  if ((rc = check_device(h->device))) return rc;
+  FCS_SET_DEVICE((h->device));
+  const size_t n = (size_t)n_reads;
+  // one H2D copy (codes, offsets, lengths, order); back come the offsets and
+  // flags, then the SMEMs and positions the totals count: nothing of the size
+  // of n_reads x max_mems leaves the device
+  Layout L;
+  const size_t ocodes = L.add((size_t)n_code_bytes), ooff = L.add(8 * n), olen = L.add(4 * n), oord = L.add(4 * n);
+  const size_t in_bytes = L.total;
+  const size_t omoff = L.add(8 * (n + 1)), oroff = L.add(8 * (n + 1)), oovf = L.add(4 * n);
+  const size_t host_bytes = L.total;
+  const size_t omems = L.add((size_t)mem_cap * sizeof(FmdIv)), opos = L.add(8 * (size_t)row_cap);
+  const FmdSeedWs W = fmd_seed_ws(L, n_reads, max_len, max_mems, row_cap);
+  SessionLease lease;
+  if ((rc = lease.acquire(h->device))) return rc;
+  Session* S = lease.get();
+  if ((rc = S->ensure_host(host_bytes)) || (rc = S->ensure_dev(L.total))) return rc;
+  if (n_code_bytes) std::memcpy(S->h<void>(ocodes), codes, (size_t)n_code_bytes);
+  std::memcpy(S->h<void>(ooff), q_off, 8 * n);
+  std::memcpy(S->h<void>(olen), q_len, 4 * n);
+  {  // longest first, as fcs_fmd_collect
+    std::vector<int32_t> start((size_t)max_len + 2, 0);
+    for (size_t r = 0; r < n; ++r) ++start[(size_t)(max_len - q_len[r]) + 1];
+    for (size_t k = 1; k < start.size(); ++k) start[k] += start[k - 1];
+    int32_t* ord = S->h<int32_t>(oord);
+    for (size_t r = 0; r < n; ++r) ord[start[(size_t)(max_len - q_len[r])]++] = (int32_t)r;
+  }
+  hipStream_t s = S->s;
+  const StreamDrain drain{s};
+  FCS_HIP_CHECK(hipMemcpyAsync(S->d<void>(0), S->h<void>(0), in_bytes, hipMemcpyHostToDevice, s));
+  // every kernel is enqueued before the first sync: the host's look at the totals does not idle the device
+  if ((rc = launch_fmd_collect(h->dx, S->d<uint8_t>(ocodes), n_code_bytes, S->d<int64_t>(ooff), S->d<int32_t>(olen),
+                               S->d<int32_t>(oord), n_reads, fmd_params(&params->collect), S->d<FmdIv>(W.arena),
+                               max_len + 1, S->d<FmdIv>(W.slots), max_mems, S->d<int32_t>(W.n_mems),
+                               S->d<int32_t>(oovf), s)) ||
+      (rc = launch_fmd_seed(h->dx, S->d<FmdIv>(W.slots), max_mems, S->d<int32_t>(W.n_mems), S->d<int32_t>(oovf), n_reads,
+                            params->max_occ, fmd_seed_steps(h, params->max_steps), S->d<FmdSeedPlace>(W.place),
+                            S->d<int32_t>(W.n_eff), S->d<int64_t>(W.n_rows), S->d<int64_t>(omoff), S->d<int64_t>(oroff),
+                            S->d<FmdIv>(omems), mem_cap, S->d<int64_t>(W.rows), S->d<int64_t>(opos), row_cap, s)))
+    return rc;
+  FCS_HIP_CHECK(hipMemcpyAsync(S->h<void>(omoff), S->d<void>(omoff), host_bytes - omoff, hipMemcpyDeviceToHost, s));
+  FCS_HIP_CHECK(hipStreamSynchronize(s));
+  std::memcpy(mem_off, S->h<void>(omoff), 8 * (n + 1));
+  std::memcpy(row_off, S->h<void>(oroff), 8 * (n + 1));
+  std::memcpy(overflow, S->h<void>(oovf), 4 * n);
+  const int64_t tm = mem_off[n], tr = row_off[n];
+  if (tm < 0 || tr < 0 || tm > (int64_t)n * max_mems)
+    return fail(FCS_ERR_DEVICE, "[E::fcs_fmd_seed] the totals came back as " + std::to_string(tm) + " SMEMs and " +
+                                    std::to_string(tr) + " rows");
+  if (tm > mem_cap || tr > row_cap) return FCS_FMD_SEED_MORE;
+  if (tm == 0 && tr == 0) return FCS_OK;
+  Layout B;
+  const size_t bmems = B.add((size_t)tm * sizeof(FmdIv)), bpos = B.add(8 * (size_t)tr);
+  if ((rc = S->ensure_host(B.total))) return rc;  // the staged inputs and offsets are spent
+  if (tm) FCS_HIP_CHECK(hipMemcpyAsync(S->h<void>(bmems), S->d<void>(omems), (size_t)tm * sizeof(FmdIv), hipMemcpyDeviceToHost, s));
+  if (tr) FCS_HIP_CHECK(hipMemcpyAsync(S->h<void>(bpos), S->d<void>(opos), 8 * (size_t)tr, hipMemcpyDeviceToHost, s));
+  FCS_HIP_CHECK(hipStreamSynchronize(s));
+  if (tm) std::memcpy(mems, S->h<void>(bmems), (size_t)tm * sizeof(FmdIv));
+  if (tr) std::memcpy(pos, S->h<void>(bpos), 8 * (size_t)tr);
+  return FCS_OK;
+}
+
+int fcs_fmd_seed_dev(const fcs_fmd_index* index, const uint8_t* dev_codes, int64_t n_code_bytes,
+                     const int64_t* dev_q_off, const int32_t* dev_q_len, const int32_t* dev_order, int32_t n_reads,
+                     int32_t max_q_len, const fcs_fmd_seed_params* params, void* dev_workspace,
+                     int64_t workspace_bytes, fcs_fmd_mem* dev_mems, int64_t mem_cap, int64_t* dev_mem_off,
+                     int64_t* dev_pos, int64_t row_cap, int64_t* dev_row_off, int32_t* dev_overflow, void* stream) {
+  if (n_reads < 0 || n_code_bytes < 0 || max_q_len < 0 || (n_code_bytes > 0 && !dev_codes) ||
+      (n_reads > 0 && (!dev_q_off || !dev_q_len || !dev_workspace)))
+    return fail(FCS_ERR_INVALID, "[E::fcs_fmd_seed_dev] bad arguments");
+  int32_t max_mems = 0;
+  int rc = fmd_seed_check(params, mem_cap, row_cap, dev_mems, dev_mem_off, dev_pos, dev_row_off, dev_overflow, n_reads,
+                          "fcs_fmd_seed_dev", max_mems);
+  if (rc) return rc;
+  Layout L;
+  const FmdSeedWs W = fmd_seed_ws(L, n_reads, max_q_len, max_mems, row_cap);
+  if (n_reads > 0 && workspace_bytes < (int64_t)L.total)
+    return fail(FCS_ERR_INVALID, "[E::fcs_fmd_seed_dev] the workspace holds " + std::to_string(workspace_bytes) +
+                                     " bytes, the call needs " + std::to_string(L.total));
+  const fcs_fmd_index* h = fmd_handle(index, "fcs_fmd_seed_dev");
+  if (!h) return FCS_ERR_INVALID;
+  if ((rc = check_device(h->device))) return rc;
+  FCS_SET_DEVICE((h->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char* ws = static_cast<char*>(dev_workspace);
+  auto at = [&](size_t off) { return static_cast<void*>(ws + off); };
+  if (n_reads > 0 &&
+      (rc = launch_fmd_collect(h->dx, dev_codes, n_code_bytes, dev_q_off, dev_q_len, dev_order, n_reads,
+                               fmd_params(&params->collect), static_cast<FmdIv*>(at(W.arena)), max_q_len + 1,
+                               static_cast<FmdIv*>(at(W.slots)), max_mems, static_cast<int32_t*>(at(W.n_mems)),
+                               dev_overflow, s)))
+    return rc;
+  if (n_reads == 0)  // only the two zero totals are written
+    return launch_fmd_seed(h->dx, nullptr, max_mems, nullptr, nullptr, 0, params->max_occ, 1, nullptr, nullptr, nullptr,
+                           dev_mem_off, dev_row_off, nullptr, mem_cap, nullptr, dev_pos, row_cap, s);
+  return launch_fmd_seed(h->dx, static_cast<FmdIv*>(at(W.slots)), max_mems, static_cast<int32_t*>(at(W.n_mems)),
+                         dev_overflow, n_reads, params->max_occ, fmd_seed_steps(h, params->max_steps),
+                         static_cast<FmdSeedPlace*>(at(W.place)), static_cast<int32_t*>(at(W.n_eff)),
+                         static_cast<int64_t*>(at(W.n_rows)), dev_mem_off, dev_row_off,
+                         reinterpret_cast<FmdIv*>(dev_mems), mem_cap, static_cast<int64_t*>(at(W.rows)), dev_pos, row_cap, s);
+}
+
 int fcs_bgzf_warmup(int32_t device, int32_t sessions, int64_t arena_bytes) {
   if (sessions < 0 || arena_bytes < 0) return fail(FCS_ERR_INVALID, "[E::fcs_bgzf_warmup] bad arguments");
   int rc = check_device(device);
@@ -2337,6 +2516,6 @@ int fcs_device_release(int32_t device) {
   return FCS_OK;
 }
 
-int fcs_abi_symbol_count(void) { return 58; }
+int fcs_abi_symbol_count(void) { return 61; }
 
 }  // extern "C"

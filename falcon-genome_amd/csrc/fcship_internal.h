@@ -298,5 +298,16 @@ int launch_fmd_collect(const FmdDevIndex& dx, const uint8_t* codes, int64_t n_co
 // (the step cap, or a row the index does not hold).
 int launch_fmd_locate(const FmdDevIndex& dx, const int64_t* rows, int64_t n, int32_t max_steps, int64_t* pos,
                       int32_t* status, hipStream_t s);
+struct FmdSeedPlace;  // fmd_expand.h: {rank, first row} of an SMEM, 16 bytes
+// After launch_fmd_collect on the same stream (fmd_seeds.hip): order, scan,
+// expand, locate.  place: max_mems entries per read; n_eff / n_rows: one per
+// read; mem_off / row_off: n_reads + 1 prefix sums, the totals last; mems /
+// pos: the compacted SMEMs and positions (-1 - row where the device did not
+// locate), written only when both totals fit mem_cap / row_cap; rows: row_cap
+// words of scratch (unused when the index has no device suffix array).
+int launch_fmd_seed(const FmdDevIndex& dx, const FmdIv* slots, int32_t max_mems, const int32_t* n_mems,
+                    const int32_t* overflow, int32_t n_reads, int32_t max_occ, int32_t max_steps, FmdSeedPlace* place,
+                    int32_t* n_eff, int64_t* n_rows, int64_t* mem_off, int64_t* row_off, FmdIv* mems, int64_t mem_cap,
+                    int64_t* rows, int64_t* pos, int64_t row_cap, hipStream_t s);
 
 }  // namespace fcs

@@ -203,6 +203,12 @@ _sig("fcs_fmd_collect_dev", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_voi
 _sig("fcs_fmd_locate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p])
 _sig("fcs_fmd_locate_dev", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_void_p])
+_sig("fcs_fmd_seed", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                               C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])
+_sig("fcs_fmd_seed_workspace_bytes", C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int64])
+_sig("fcs_fmd_seed_dev", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p])
 _sig("fcs_synth_phmm_sizes", C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, i64p, i64p])
 _sig("fcs_synth_phmm", C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 10)
 _sig("fcs_synth_bsw_sizes", C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
@@ -675,3 +681,43 @@ def fmd_locate(handle, rows, max_steps: int = 0):
     pos, status = np.zeros(len(rows), np.int64), np.zeros(len(rows), np.int32)
     check(lib.fcs_fmd_locate(handle, rows.ctypes.data, len(rows), max_steps, pos.ctypes.data, status.ctypes.data))
     return pos, status
+
+
+FCS_FMD_SEED_MORE = 1
+
+
+class FmdSeedParams(C.Structure):
+    _fields_ = [("collect", FmdParams), ("max_occ", C.c_int32), ("max_steps", C.c_int32)]
+
+
+def fmd_seed(handle, codes, q_off, q_len, min_len=19, split_len=28, split_width=10, max_mem_intv=20,
+             max_mems=FCS_FMD_MAX_MEMS_DEFAULT, max_occ=500, max_steps=0, mem_cap=None, row_cap=None, mems=None,
+             pos=None):
+    """fcs_fmd_seed: (mems, mem_off, pos, row_off, overflow, status).  status is
+    FCS_OK (mems / pos hold mem_off[-1] / row_off[-1] entries) or
+    FCS_FMD_SEED_MORE (the totals exceed a capacity: mems / pos are as they
+    were passed in, and the caller repeats the call with at least the
+    totals); nothing is retried here.  Capacities default to a first guess of
+    16 SMEMs and 64 rows per read; mems / pos may be passed in (of at least the
+    capacities) to see what the call writes."""
+    codes = np.ascontiguousarray(codes, np.uint8)
+    q_off = np.ascontiguousarray(q_off, np.int64)
+    q_len = np.ascontiguousarray(q_len, np.int32)
+    n = len(q_len)
+    mem_cap = max(16 * n, 4096) if mem_cap is None else int(mem_cap)
+    row_cap = max(64 * n, 65536) if row_cap is None else int(row_cap)
+    if mems is None:
+        mems = np.zeros(max(mem_cap, 1), FMD_MEM)
+    if pos is None:
+        pos = np.zeros(max(row_cap, 1), np.int64)
+    assert mems.dtype == FMD_MEM and pos.dtype == np.int64 and len(mems) >= mem_cap and len(pos) >= row_cap
+    mem_off, row_off = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+    overflow = np.zeros(max(n, 1), np.int32)
+    P = FmdSeedParams(FmdParams(min_len, split_len, split_width, max_mems, max_mem_intv), max_occ, max_steps)
+    rc = lib.fcs_fmd_seed(handle, codes.ctypes.data, len(codes), q_off.ctypes.data, q_len.ctypes.data, n,
+                          C.addressof(P), mems.ctypes.data, mem_cap, mem_off.ctypes.data, pos.ctypes.data, row_cap,
+                          row_off.ctypes.data, overflow.ctypes.data)
+    if rc == FCS_FMD_SEED_MORE:
+        return mems, mem_off, pos, row_off, overflow[:n], rc
+    check(rc)
+    return mems[:mem_off[-1]], mem_off, pos[:row_off[-1]], row_off, overflow[:n], rc

@@ -171,13 +171,13 @@ SeedParams seed_params(const AlignOptions& opt) {
 // occurrences, chains and their filter.  pos: SA[m.k + j] of those occurrences
 // in the loop's order (the device path, host/gpu_seed.h), or null: located on
 // the host index.
-void chain_read(const KmerIndex& idx, const AlignOptions& opt, ReadAln& R, const std::vector<BiInterval>& mems,
+void chain_read(const KmerIndex& idx, const AlignOptions& opt, ReadAln& R, const BiInterval* mems, size_t n_mems,
                 const int64_t* pos) {
   const int L = (int)R.code[0].size();
   {  // bwa mem_chain's frac_rep: the union of the query spans of SMEMs with > max_occ hits
     std::vector<std::pair<int, int>> rep;
-    for (const BiInterval& m : mems)
-      if (m.s > opt.max_occ) rep.emplace_back(m.qb, m.qe);
+    for (size_t i = 0; i < n_mems; ++i)
+      if (mems[i].s > opt.max_occ) rep.emplace_back(mems[i].qb, mems[i].qe);
     std::sort(rep.begin(), rep.end());
     int b = 0, e = 0, l_rep = 0;
     for (const auto& [sb, se] : rep) {
@@ -188,7 +188,8 @@ void chain_read(const KmerIndex& idx, const AlignOptions& opt, ReadAln& R, const
     R.frac_rep = L ? (double)l_rep / L : 0.;
   }
   std::vector<Seed> seeds;
-  for (const BiInterval& m : mems) {
+  for (size_t i = 0; i < n_mems; ++i) {
+    const BiInterval& m = mems[i];
     const int64_t step = m.s > opt.max_occ ? m.s / opt.max_occ : 1;
     for (int64_t j = 0, kept = 0; j < m.s && kept < opt.max_occ; j += step, ++kept) {
       Seed sd;
@@ -288,7 +289,7 @@ void seed_read(const KmerIndex& idx, const AlignOptions& opt, ReadAln& R) {
   const SeedParams P = seed_params(opt);
   std::vector<BiInterval> mems;
   idx.fmd().collect(q.data(), (int)q.size(), P.min_len, P.split_len, P.split_width, P.max_mem_intv, mems);
-  chain_read(idx, opt, R, mems, nullptr);
+  chain_read(idx, opt, R, mems.data(), mems.size(), nullptr);
 }
 
 // mem_chain2aln's test: is seed s (almost) inside a region already made? (then
@@ -1204,16 +1205,17 @@ void align_batch(const KmerIndex& idx, const std::vector<std::string>& seqs, con
     R.code[1] = encode(R.seq[1]);
     if (!opt.gpu_seed) seed_read(idx, opt, R);
   });
-  if (opt.gpu_seed && !reads.empty()) {  // one collect and one locate call for the chunk, then chaining per read
+  // one collect and one locate call for the chunk (fused: one call for both), then chaining per read
+  if (opt.gpu_seed && !reads.empty()) {
     std::vector<const uint8_t*> q(reads.size());
     std::vector<int> qlen(reads.size());
     for (size_t r = 0; r < reads.size(); ++r) q[r] = reads[r].code[0].data(), qlen[r] = (int)reads[r].code[0].size();
     SeedBatch sb;
     gpu_seed_batch(idx.fmd(), idx.device_fmd(opt.gpu), q.data(), qlen.data(), reads.size(), seed_params(opt),
-                   opt.threads, sb);
+                   opt.threads, sb, opt.gpu_seed_fused);
     const uint64_t tc = now_us();
     parallel_for(reads.size(), opt.threads,
-                 [&](size_t r) { chain_read(idx, opt, reads[r], sb.mems[r], sb.pos[r].data()); });
+                 [&](size_t r) { chain_read(idx, opt, reads[r], sb.mems_of(r), sb.n_mems_of(r), sb.pos_of(r)); });
     st.seed_collect_seconds += sb.collect_seconds;
     st.seed_locate_seconds += sb.locate_seconds;
     st.seed_chain_seconds += (now_us() - tc) / 1e6;
@@ -1548,6 +1550,7 @@ AlignStats align_fastq(const AlignJob& job, const std::vector<int>& devices, std
   base.chunk_size = conf().get_int("bwa.chunk_size");
   const bool want_gpu_seed = conf().get_bool("bwa.gpu_seed");
   base.gpu_seed = want_gpu_seed && gpu_seed_available();
+  base.gpu_seed_fused = base.gpu_seed && conf().get_bool("bwa.gpu_seed_fused") && gpu_seed_fused_available();
   if (want_gpu_seed && !base.gpu_seed) {
     static std::once_flag said;
     std::call_once(said, [] {
@@ -1758,8 +1761,10 @@ AlignStats align_fastq(const AlignJob& job, const std::vector<int>& devices, std
       << ", records " << tot.record_seconds << "), sort + BAM + index " << (t_end - t_aln) / 1e6 << " s\n";
   if (base.gpu_seed)
     rep << "[fcs-genome align] GPU seeding (bwa.gpu_seed): " << tot.seed_gpu_reads << " reads through the device, "
-        << tot.seed_host_reads << " of them collected on the host (more than " << base.seed_max_mems
-        << " SMEMs), " << tot.seed_host_rows << " rows located on the host; seeding thread-seconds: collect "
+        << tot.seed_host_reads << " of them collected on the host (more than " << base.seed_max_mems << " SMEMs"
+        << (base.gpu_seed_fused ? "; fused: one fcs_fmd_seed call per chunk, under collect, its host repair pass under locate"
+                                : "")
+        << "), " << tot.seed_host_rows << " rows located on the host; seeding thread-seconds: collect "
         << tot.seed_collect_seconds << ", locate " << tot.seed_locate_seconds << ", chain " << tot.seed_chain_seconds
         << "\n";
   report = rep.str();

@@ -63,6 +63,7 @@ struct AlignOptions {
   int pen_unpaired = 17;     // bwa -U
   int max_matesw = 50;       // bwa max_matesw: rescue anchors per read
   bool gpu_seed = false;     // bwa.gpu_seed: SMEM collection and SA lookups of a chunk on the GPU (host/gpu_seed.h)
+  bool gpu_seed_fused = false;  // bwa.gpu_seed_fused: one fcs_fmd_seed call per chunk, compacted output
   int seed_max_mems = 32;    // device SMEM slots per read (1 KB); a read with more is collected on the host
   int64_t read_id0 = 0;      // index of the batch's first read (pair) in the input: bwa's hash seed for ties
   std::string rg = "sample", sample = "sample", platform = "illumina", library = "sample";

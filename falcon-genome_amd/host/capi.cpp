@@ -169,6 +169,12 @@ int fcsg_fmd_smems(const uint8_t* ref, const int64_t* clen, int ncontig, const u
   return rc < 0 ? rc : n;
 }
 
+int fcsg_fmd_seeds(const uint8_t* ref, const int64_t* clen, int ncontig, const uint8_t* q, const int64_t* qoff,
+                   const int32_t* qlen, int n, int min_len, int split_len, int split_width, int max_mem_intv,
+                   int max_occ, int sa_intv, const char* index_path, int mode, int max_mems, int max_steps,
+                   int64_t start_mem_cap, int64_t start_row_cap, int64_t* mems, int64_t* mem_off, int32_t* n_mems,
+                   int64_t mem_cap, int64_t* loc, int64_t* loc_off, int32_t* n_loc, int64_t loc_cap, int64_t* stats);
+
 // The aligner's seeding of a batch of reads (codes 0..4, read r at q[qoff[r] ..
 // qoff[r] + qlen[r])) on an FMD-index of the given contigs, on the host index
 // (gpu 0: FmdIndex::collect / locate) or through the device entry points (gpu
@@ -184,6 +190,25 @@ int fcsg_fmd_seed_batch(const uint8_t* ref, const int64_t* clen, int ncontig, co
                         int max_occ, int sa_intv, const char* index_path, int gpu, int max_mems, int64_t* mems,
                         int64_t* mem_off, int32_t* n_mems, int64_t mem_cap, int64_t* loc, int64_t* loc_off,
                         int32_t* n_loc, int64_t loc_cap, int64_t* fallback) {
+  int64_t stats[3] = {0, 0, 0};
+  const int rc = fcsg_fmd_seeds(ref, clen, ncontig, q, qoff, qlen, n, min_len, split_len, split_width, max_mem_intv,
+                                max_occ, sa_intv, index_path, gpu ? 1 : 0, max_mems, 0, 0, 0, mems, mem_off, n_mems,
+                                mem_cap, loc, loc_off, n_loc, loc_cap, stats);
+  if (rc == 0) *fallback = stats[0];
+  return rc;
+}
+
+// fcsg_fmd_seed_batch with the path chosen by mode: 0 the host index, 1 the
+// two-call device path (fcs_fmd_collect, fcs_fmd_locate), 2 the fused call
+// (fcs_fmd_seed) with the device's LF-step cap max_steps (0: its default) and
+// the capacities start_mem_cap / start_row_cap for its first call (0: the
+// aligner's).  stats = {reads collected on the host, rows located on the host,
+// fused calls repeated with more room}.
+int fcsg_fmd_seeds(const uint8_t* ref, const int64_t* clen, int ncontig, const uint8_t* q, const int64_t* qoff,
+                   const int32_t* qlen, int n, int min_len, int split_len, int split_width, int max_mem_intv,
+                   int max_occ, int sa_intv, const char* index_path, int mode, int max_mems, int max_steps,
+                   int64_t start_mem_cap, int64_t start_row_cap, int64_t* mems, int64_t* mem_off, int32_t* n_mems,
+                   int64_t mem_cap, int64_t* loc, int64_t* loc_off, int32_t* n_loc, int64_t loc_cap, int64_t* stats) {
   return guard([&] {
     std::vector<std::vector<uint8_t>> cs;
     int64_t o = 0;
@@ -202,14 +227,17 @@ int fcsg_fmd_seed_batch(const uint8_t* ref, const int64_t* clen, int ncontig, co
     SeedParams P;
     P.min_len = min_len, P.split_len = split_len, P.split_width = split_width, P.max_mem_intv = max_mem_intv;
     P.max_occ = max_occ, P.max_mems = max_mems;
+    P.max_steps = max_steps, P.mem_cap = start_mem_cap, P.row_cap = start_row_cap;
     if (max_occ < 1) throw invalidParam("fcsg_fmd_seed_batch: max_occ");
+    if (mode < 0 || mode > 2) throw invalidParam("fcsg_fmd_seeds: mode");
     SeedBatch sb;
-    if (gpu) {
+    if (mode) {
       if (!gpu_seed_available()) throw internalError("fcsg_fmd_seed_batch: libfcship has no fcs_fmd_* entry points");
+      if (mode == 2 && !gpu_seed_fused_available()) throw internalError("fcsg_fmd_seeds: libfcship has no fcs_fmd_seed");
       FmdDeviceCopies dev(fmd);
       std::vector<const uint8_t*> qp(n);
       for (int r = 0; r < n; ++r) qp[r] = q + qoff[r];
-      gpu_seed_batch(fmd, dev.get(0), qp.data(), qlen, (size_t)n, P, 4, sb);
+      gpu_seed_batch(fmd, dev.get(0), qp.data(), qlen, (size_t)n, P, 4, sb, mode == 2);
     } else {
       sb.mems.resize(n);
       for (int r = 0; r < n; ++r)
@@ -219,8 +247,11 @@ int fcsg_fmd_seed_batch(const uint8_t* ref, const int64_t* clen, int ncontig, co
     int64_t nm = 0, nl = 0;
     for (int r = 0; r < n; ++r) {
       mem_off[r] = nm, loc_off[r] = nl;
-      const int64_t* pos = gpu ? sb.pos[r].data() : nullptr;
-      for (const BiInterval& m : sb.mems[r]) {
+      const int64_t* pos = mode ? sb.pos_of((size_t)r) : nullptr;  // null: a read of the host's
+      const BiInterval* rm = mode ? sb.mems_of((size_t)r) : sb.mems[r].data();
+      const size_t rn = mode ? sb.n_mems_of((size_t)r) : sb.mems[r].size();
+      for (size_t i = 0; i < rn; ++i) {
+        const BiInterval& m = rm[i];
         if (nm >= mem_cap) throw invalidParam("fcsg_fmd_seed_batch: SMEM capacity");
         int64_t* w = mems + 5 * nm++;
         w[0] = m.qb, w[1] = m.qe, w[2] = m.s, w[3] = m.k, w[4] = m.l;
@@ -230,7 +261,7 @@ int fcsg_fmd_seed_batch(const uint8_t* ref, const int64_t* clen, int ncontig, co
           int c;
           int64_t off;
           bool rev;
-          if (gpu) map.locate(*pos++, m.qe - m.qb, c, off, rev);
+          if (pos) map.locate(*pos++, m.qe - m.qb, c, off, rev);
           else fmd.locate(m, j, c, off, rev);
           int64_t* l = loc + 3 * nl++;
           l[0] = c, l[1] = off, l[2] = rev;
@@ -240,7 +271,7 @@ int fcsg_fmd_seed_batch(const uint8_t* ref, const int64_t* clen, int ncontig, co
       n_loc[r] = (int32_t)(nl - loc_off[r]);
     }
     mem_off[n] = nm, loc_off[n] = nl;
-    *fallback = sb.host_reads;
+    stats[0] = sb.host_reads, stats[1] = sb.host_rows, stats[2] = sb.retries;
   });
 }
 

@@ -38,6 +38,8 @@ void Config::init(const std::string& root_dir) {
   declare("bwa.chunk_size", "100000", "reads per SW batch handed to the GPU");
   declare("bwa.gpu_seed", "false",
           "collect SMEMs and locate their occurrences on the GPU (one call each per chunk) instead of on the host threads");
+  declare("bwa.gpu_seed_fused", "true",
+          "with bwa.gpu_seed: one fused call per chunk (order, expand and locate on the GPU, compacted copy back) instead of two");
   declare("bwa.gpu_slots", "0", "aligner host threads (chunks in flight) per GPU; 0: host threads / GPUs, at least 4");
   declare("gatk.intv.path", "", "default path to existing contig intervals");
   declare("gatk.ncontigs", "32", "contig partition num in htc/mutect2");

@@ -3,6 +3,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <set>
 
@@ -20,6 +21,7 @@ struct SeedApi {
   decltype(&fcs_fmd_index_destroy) destroy = nullptr;
   decltype(&fcs_fmd_collect) collect = nullptr;
   decltype(&fcs_fmd_locate) locate = nullptr;
+  decltype(&fcs_fmd_seed) seed = nullptr;  // optional: the fused mode
   const char* (*last_error)() = nullptr;
   bool ok() const { return create && destroy && collect && locate && last_error; }
 };
@@ -31,6 +33,7 @@ const SeedApi& seed_api() {
     a.destroy = reinterpret_cast<decltype(a.destroy)>(dlsym(RTLD_DEFAULT, "fcs_fmd_index_destroy"));
     a.collect = reinterpret_cast<decltype(a.collect)>(dlsym(RTLD_DEFAULT, "fcs_fmd_collect"));
     a.locate = reinterpret_cast<decltype(a.locate)>(dlsym(RTLD_DEFAULT, "fcs_fmd_locate"));
+    a.seed = reinterpret_cast<decltype(a.seed)>(dlsym(RTLD_DEFAULT, "fcs_fmd_seed"));
     a.last_error = reinterpret_cast<decltype(a.last_error)>(dlsym(RTLD_DEFAULT, "fcs_last_error"));
     return a;
   }();
@@ -46,6 +49,7 @@ std::set<FmdDeviceCopies*>& live_copies() {
 }  // namespace
 
 bool gpu_seed_available() { return seed_api().ok(); }
+bool gpu_seed_fused_available() { return seed_api().ok() && seed_api().seed; }
 
 FmdDeviceCopies::FmdDeviceCopies(const FmdIndex& fmd) : fmd_(fmd) {
   std::lock_guard<std::mutex> g(g_copies_mu);
@@ -108,11 +112,98 @@ void TextMap::locate(int64_t p, int len, int& contig, int64_t& off, bool& rev) c
   off = p - cstart_[contig];
 }
 
-void gpu_seed_batch(const FmdIndex& fmd, fcs_fmd_index* dev, const uint8_t* const* q, const int* qlen, size_t n,
+namespace {
+
+// One fcs_fmd_seed call for the chunk (a second one when the first reports
+// larger totals than its capacities), then one pass over the reads for what
+// the device left: rows it did not locate, reads it handed back.
+void gpu_seed_fused(const FmdIndex& fmd, fcs_fmd_index* dev, const uint8_t* const* q, const int* qlen, size_t n,
                     const SeedParams& P, int threads, SeedBatch& out) {
+  const SeedApi& A = seed_api();
+  const uint64_t t0 = now_us();
+  out.fused = true;
+  out.mems.assign(n, {});
+  out.pos.clear();
+  out.mem_off.assign(n + 1, 0);
+  out.row_off.assign(n + 1, 0);
+  out.overflow.assign(n, 0);
+  std::vector<int64_t> q_off(n + 1, 0);
+  std::vector<int32_t> q_len(n);
+  for (size_t r = 0; r < n; ++r) q_len[r] = qlen[r], q_off[r + 1] = q_off[r] + qlen[r];
+  std::vector<uint8_t> codes((size_t)q_off[n]);
+  parallel_for(n, threads, [&](size_t r) {
+    if (qlen[r]) std::memcpy(codes.data() + q_off[r], q[r], (size_t)qlen[r]);
+  });
+  fcs_fmd_seed_params sp;
+  sp.collect.min_len = P.min_len;
+  sp.collect.split_len = P.split_len;
+  sp.collect.split_width = P.split_width;
+  sp.collect.max_mems = P.max_mems;
+  sp.collect.max_mem_intv = P.max_mem_intv;
+  sp.max_occ = P.max_occ;
+  sp.max_steps = P.max_steps;
+  int64_t mem_cap = P.mem_cap > 0 ? P.mem_cap : std::max<int64_t>(16 * (int64_t)n, 4096);
+  int64_t row_cap = P.row_cap > 0 ? P.row_cap : std::max<int64_t>(64 * (int64_t)n, 65536);
+  for (int attempt = 0;; ++attempt) {
+    out.flat_mems.reset((size_t)mem_cap);
+    out.flat_pos.reset((size_t)row_cap);
+    const int rc = A.seed(dev, codes.data(), (int64_t)codes.size(), q_off.data(), q_len.data(), (int32_t)n, &sp,
+                          reinterpret_cast<fcs_fmd_mem*>(out.flat_mems.data()), mem_cap, out.mem_off.data(),
+                          out.flat_pos.data(), row_cap, out.row_off.data(), out.overflow.data());
+    if (rc == FCS_OK) break;
+    if (rc != FCS_FMD_SEED_MORE) throw failedCommand(std::string("[E::fcs-genome align] fcs_fmd_seed: ") + A.last_error());
+    if (attempt > 0) throw internalError("[E::fcsg] fcs_fmd_seed asked for more room twice");
+    mem_cap = std::max(mem_cap, out.mem_off[n]);  // the totals it reported
+    row_cap = std::max(row_cap, out.row_off[n]);
+    ++out.retries;
+  }
+  out.rows = out.row_off[n];
+  const uint64_t t1 = now_us();
+  out.collect_seconds = (t1 - t0) / 1e6;
+  const FmdView v = fmd.view();
+  fcs::FmdIx<fcs::FmdHostFetch> ix;
+  ix.f.occ = v.occ;
+  ix.n = v.n_rows;
+  ix.C = v.C;
+  std::vector<int64_t> host_rows(n, 0);
+  std::atomic<int64_t> lost{-1};  // a row neither side can locate (the pass runs on threads: reported after it)
+  parallel_for(n, threads, [&](size_t r) {
+    if (out.overflow[r]) {  // its positions come from FmdIndex::locate in chain_read
+      fmd.collect(q[r], qlen[r], P.min_len, P.split_len, P.split_width, P.max_mem_intv, out.mems[r]);
+      return;
+    }
+    for (int64_t i = out.row_off[r]; i < out.row_off[r + 1]; ++i) {
+      int64_t& p = out.flat_pos.data()[i];
+      if (p >= 0) continue;
+      const int64_t row = -1 - p;
+      if (v.sa_intv == 1) {  // the full suffix array stayed on the host
+        if (row >= v.n_sa) lost = row;
+        else p = (int64_t)v.sa[row];
+        continue;
+      }
+      int32_t steps;
+      if (fcs::fmd_sa_walk(ix, v.sa, v.n_sa, v.sa_intv, v.special, v.n_special, row, INT32_MAX, p, steps) !=
+          fcs::kFmdLocated)
+        lost = row;
+      ++host_rows[r];
+    }
+  });
+  if (lost >= 0) throw internalError("[E::fcsg] FMD-index row " + std::to_string(lost.load()) + " cannot be located");
+  for (size_t r = 0; r < n; ++r) out.host_reads += out.overflow[r] != 0, out.host_rows += host_rows[r];
+  out.locate_seconds = (now_us() - t1) / 1e6;
+}
+
+}  // namespace
+
+void gpu_seed_batch(const FmdIndex& fmd, fcs_fmd_index* dev, const uint8_t* const* q, const int* qlen, size_t n,
+                    const SeedParams& P, int threads, SeedBatch& out, bool fused) {
   const SeedApi& A = seed_api();
   if (!A.ok()) throw internalError("[E::fcsg] GPU seeding without its entry points");
   if (P.max_mems < 1 || P.max_occ < 1) throw invalidParam("GPU seeding: max_mems and max_occ must be at least 1");
+  if (fused) {
+    if (!A.seed) throw internalError("[E::fcsg] fused GPU seeding without fcs_fmd_seed");
+    return gpu_seed_fused(fmd, dev, q, qlen, n, P, threads, out);
+  }
   const uint64_t t0 = now_us();
   out.mems.assign(n, {});
   out.pos.assign(n, {});

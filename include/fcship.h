@@ -464,7 +464,38 @@ int fcs_bgzf_deflate_dev(const uint8_t* dev_data, int64_t n_bytes, int32_t block
  * FCS_FMD_LOCATED, by at most max_steps LF steps to a sampled or special row
  * (0: 32 * sa_intv; a walk ends at each step with probability 1 / sa_intv,
  * so about e^-32 of the rows run into that cap); FCS_FMD_STEP_CAP rows, and
- * FCS_FMD_BAD_ROW ones (outside the index), are left to the caller. */
+ * FCS_FMD_BAD_ROW ones (outside the index), are left to the caller.
+ *
+ * fcs_fmd_seed: collect and locate in one call, host buffers, synchronous;
+ * what comes back is compacted.  On the device, after the collect: each read's
+ * SMEMs are ordered by (qb, qe), the SMEM and row counts are prefix-summed,
+ * the rows of the occurrences bwa samples (at most max_occ per SMEM: rows k,
+ * k + step, .. with step = s / max_occ beyond max_occ) are written out SMEM by
+ * SMEM and located.  Read r's SMEMs are mems[mem_off[r] .. mem_off[r + 1]) in
+ * (qb, qe) order and its positions pos[row_off[r] .. row_off[r + 1]) in that
+ * order, occurrence by occurrence; mem_off[n_reads] and row_off[n_reads] are
+ * the totals.  pos[i] >= 0 is the text position SA[row]; a row the device did
+ * not locate (the step cap, a bad row, or an index made without its suffix
+ * array, whose owner reads SA[row] itself) comes back as -1 - row.  A read
+ * the device hands back (as in fcs_fmd_collect) has overflow[r] = 1 and empty
+ * ranges.  mem_off, row_off and overflow are always written in full; when a
+ * total exceeds mem_cap or row_cap the call returns FCS_FMD_SEED_MORE, has
+ * written nothing to mems / pos, and is repeated with capacities of at least
+ * the totals.  It copies back the offsets and flags, then exactly 32
+ * mem_off[n_reads] + 8 row_off[n_reads] bytes.
+ *
+ * fcs_fmd_seed_dev: the same with device buffers, stream-ordered, no sync;
+ * the totals stay in dev_mem_off[n_reads] / dev_row_off[n_reads], and no write
+ * goes beyond a capacity.  dev_workspace holds
+ * fcs_fmd_seed_workspace_bytes(n_reads, max_q_len, max_mems, row_cap) bytes,
+ * the sum of these parts, each rounded up to a multiple of 256:
+ *   fcs_fmd_collect_arena_bytes(n_reads, max_q_len)   the interval stacks
+ *   32 n_reads max_mems                               the collect's slots
+ *   16 n_reads max_mems                               each SMEM's rank and first row
+ *   4 n_reads, 4 n_reads, 8 n_reads                   SMEMs collected, SMEMs kept, rows per read
+ *   8 row_cap                                         the rows before they are located
+ * (1 read of 151 bases, 32 slots, 1024 rows: 622592 + 1024 + 512 + 256 + 256
+ * + 256 + 8192 = 633088). */
 typedef struct fcs_fmd_index fcs_fmd_index;
 typedef struct {
   int64_t k, l, s; /* SA interval [k, k + s) of the match, [l, l + s) of its reverse complement */
@@ -497,6 +528,22 @@ int fcs_fmd_locate(const fcs_fmd_index* index, const int64_t* rows, int64_t n, i
                    int32_t* status);
 int fcs_fmd_locate_dev(const fcs_fmd_index* index, const int64_t* dev_rows, int64_t n, int32_t max_steps,
                        int64_t* dev_pos, int32_t* dev_status, void* stream);
+#define FCS_FMD_SEED_MORE 1 /* not a failure: the totals exceed a capacity; only totals/offsets/flags were written */
+typedef struct {
+  fcs_fmd_params collect; /* as fcs_fmd_collect; max_mems = device slots per read */
+  int32_t max_occ;        /* >= 1: occurrences located per SMEM, sampled beyond (bwa -c) */
+  int32_t max_steps;      /* as fcs_fmd_locate; 0: 32 * sa_intv */
+} fcs_fmd_seed_params;
+int fcs_fmd_seed(const fcs_fmd_index* index, const uint8_t* codes, int64_t n_code_bytes, const int64_t* q_off,
+                 const int32_t* q_len, int32_t n_reads, const fcs_fmd_seed_params* params, fcs_fmd_mem* mems,
+                 int64_t mem_cap, int64_t* mem_off, int64_t* pos, int64_t row_cap, int64_t* row_off,
+                 int32_t* overflow);
+int64_t fcs_fmd_seed_workspace_bytes(int32_t n_reads, int32_t max_q_len, int32_t max_mems, int64_t row_cap);
+int fcs_fmd_seed_dev(const fcs_fmd_index* index, const uint8_t* dev_codes, int64_t n_code_bytes,
+                     const int64_t* dev_q_off, const int32_t* dev_q_len, const int32_t* dev_order, int32_t n_reads,
+                     int32_t max_q_len, const fcs_fmd_seed_params* params, void* dev_workspace,
+                     int64_t workspace_bytes, fcs_fmd_mem* dev_mems, int64_t mem_cap, int64_t* dev_mem_off,
+                     int64_t* dev_pos, int64_t row_cap, int64_t* dev_row_off, int32_t* dev_overflow, void* stream);
 
 /* ---------------------------------------------- synthetic workload builders */
 /* Seeded generators for the benchmark configurations (BASELINE.json C2/C3).

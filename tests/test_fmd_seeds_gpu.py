@@ -1,0 +1,295 @@
+"""The fused seeding call on the GPU (fcs_fmd_seed): collect, then
+fmd_seed_order_kernel, fmd_seed_scan_kernel, fmd_seed_expand_kernel and
+fmd_seed_locate_kernel (falcon-genome_amd/csrc/fmd_seeds.hip) on one stream,
+and a compacted copy back.  fcsg_fmd_seeds(mode=2), the aligner's fused path
+(host/gpu_seed.cpp), must return every integer mode 0 (FmdIndex::collect /
+locate, pinned to a brute-force definition by test_fmindex.py) returns, and
+its stats say what went to the host; the ctypes binding is checked against
+the same host answer through the full suffix array.  The batches are those of
+fmd_seed_cases.py, which test_fmd_seeds_cpu.py runs through the host build of
+the same per-read code."""
+import re
+import threading
+
+import numpy as np
+import pytest
+
+import fcship
+import fmd_seed_cases as S
+import fmd_seeds_cases as F
+import host_lib as H
+
+pytestmark = pytest.mark.gpu
+
+ENV = {"FCS_GPU_DEVICES": "0"}
+SAMPLED = dict(params=(5, 28, 10, 20), max_occ=3)   # SMEMs with tens of occurrences, three of them located
+
+
+@pytest.fixture(scope="module")
+def host_plain():
+    """The host's answer for the plain batch at each parameter set, computed once."""
+    return {P: S.seed_batch(S.plain_ref(), S.plain_batch(), 0, P) for P in S.PARAM_SETS}
+
+
+@pytest.fixture(scope="module")
+def host_sampled():
+    want = S.seed_batch(S.plain_ref(), S.plain_batch()[:120], 0, sa_intv=1, **SAMPLED)
+    assert any((m[:, 2] > 3).any() for m in want[0] if len(m))   # the sampling branch runs
+    return want
+
+
+@pytest.fixture(scope="module")
+def index8():
+    """A device copy of the plain reference's index at sa_intv 8, and its full suffix array."""
+    contigs = S.plain_ref()
+    sa1 = S.index_arrays(contigs, 1)[3].astype(np.int64)
+    occ, Carr, n_rows, sa, rows, ssa, flen = S.index_arrays(contigs, 8)
+    h = fcship.fmd_index_create(occ, Carr, n_rows, sa, 8, rows, ssa, flen)
+    yield h, sa1
+    fcship.fmd_index_destroy(h)
+
+
+def prefix(result, n):
+    return result[0][:n], result[1][:n], result[2]
+
+
+def flat(host_mems, sa1, max_occ=500):
+    """fcs_fmd_seed's output for reads whose host SMEM lists ({qb, qe, s, k, l} rows)
+    are host_mems: (mems, mem_off, pos, row_off), the positions read from the
+    full suffix array at the rows bwa samples."""
+    counts = [len(m) for m in host_mems]
+    allm = np.concatenate([m.reshape(-1, 5) for m in host_mems] + [np.zeros((0, 5), np.int64)])
+    mems = np.zeros(len(allm), fcship.FMD_MEM)
+    for j, f in enumerate(("qb", "qe", "s", "k", "l")):
+        mems[f] = allm[:, j]
+    s, k = allm[:, 2], allm[:, 3]
+    kept = np.minimum(s, max_occ)
+    step = np.where(s > max_occ, s // max_occ, 1)
+    rows = np.repeat(k, kept) + (np.arange(kept.sum()) - np.repeat(np.cumsum(kept) - kept, kept)) * np.repeat(step, kept)
+    mem_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    row_off = np.concatenate([[0], np.cumsum(kept)])[mem_off].astype(np.int64)
+    return mems, mem_off, sa1[rows.astype(np.int64)], row_off
+
+
+def assert_flat(got, want):
+    mems, mem_off, pos, row_off = got[:4]
+    assert np.array_equal(mem_off, want[1]) and np.array_equal(row_off, want[3])
+    assert np.array_equal(mems, want[0]) and np.array_equal(pos, want[2])
+
+
+@pytest.mark.parametrize("n", [1, 15, 16, 17, 63, 64, 65, len(S.plain_batch())])
+def test_plain_batch_sizes(gpu, host_plain, n):
+    """1, 15, 16, 17 reads (a collect wave holds 16 quads), 63, 64, 65 (a
+    collect block holds 64; the order kernel takes four reads per wave) and the
+    whole batch, bwa's parameters: equal, nothing went to the host, no retry."""
+    got = F.seeds(S.plain_ref(), S.plain_batch()[:n], F.FUSED, S.BWA)
+    S.assert_same(got, prefix(host_plain[S.BWA], n))
+    assert got[3] == [0, 0, 0]
+
+
+def tiled(host, reads, order):
+    """The host's result for reads[i] for i in order."""
+    return [host[0][i] for i in order], [host[1][i] for i in order], 0
+
+
+@pytest.mark.parametrize("n", [1023, 1024, 1025, 2300])
+def test_scan_edges(gpu, host_plain, n):
+    """The plain batch repeated: one read per scan lane, then the first size at
+    which a lane sums two reads, and several reads per lane."""
+    reads = S.plain_batch()
+    order = [i % len(reads) for i in range(n)]
+    got = F.seeds(S.plain_ref(), [reads[i] for i in order], F.FUSED, S.BWA, mem_cap=1 << 18)
+    S.assert_same(got, tiled(host_plain[S.BWA], reads, order))
+    assert got[3] == [0, 0, 0]
+
+
+def test_scan_edges_empty_reads_and_offsets(gpu, host_plain, index8):
+    """All-N reads (no SMEM) and zero-length reads first, last and at positions
+    1,023 and 1,024 of 2,049 reads, through the binding: mem_off and row_off are
+    the host's cumulative counts, and the content is the host's."""
+    h, sa1 = index8
+    reads = S.plain_batch()
+    n = 2049
+    order = [i % len(reads) for i in range(n)]
+    batch = [reads[i] for i in order]
+    host_mems = [host_plain[S.BWA][0][i] for i in order]
+    empty = np.zeros((0, 5), np.int64)
+    for at, q in ((0, "N" * 40), (1, ""), (1023, ""), (1024, "N" * 151), (n - 2, "N"), (n - 1, "")):
+        batch[at], host_mems[at] = q, empty
+    got = fcship.fmd_seed(h, *S.soa(batch))
+    assert got[5] == fcship.FCS_OK and not got[4].any()
+    want = flat(host_mems, sa1)
+    assert want[1][-1] > 2049 and want[3][-1] >= want[1][-1]
+    assert_flat(got, want)
+    for at in (0, 1, 1023, 1024, n - 2, n - 1):
+        assert got[1][at] == got[1][at + 1] and got[3][at] == got[3][at + 1]
+
+
+@pytest.mark.parametrize("P", S.PARAM_SETS[1:], ids=["min_len1", "no_reseed", "no_third_round"])
+def test_plain_batch_parameters(gpu, host_plain, P):
+    """min_len 1 (up to 114 SMEMs per read: a lane of the order kernel ranks
+    several, over two tiles), split_len 10^9, max_mem_intv 0."""
+    got = F.seeds(S.plain_ref(), S.plain_batch(), F.FUSED, P)
+    S.assert_same(got, host_plain[P])
+    # nothing for the host; one repeat exactly when the totals exceed the aligner's first capacities
+    n = len(S.plain_batch())
+    smems, rows = sum(len(m) for m in host_plain[P][0]), sum(len(x) for x in host_plain[P][1])
+    assert got[3] == [0, 0, int(smems > max(16 * n, 4096) or rows > max(64 * n, 65536))]
+    if P[0] == 1:
+        assert max(len(m) for m in host_plain[P][0]) > 64 and got[3][2] == 1
+
+
+def test_low_complexity(gpu):
+    """One read ranks about 2,700 SMEMs at max_mems 4096 and nothing goes to the
+    host; at the default 128 the reads with more are the host's, and only they."""
+    want = S.seed_batch(S.low_ref(), S.low_batch(), 0)
+    counts = [len(m) for m in want[0]]
+    assert max(counts) > 2000
+    got = F.seeds(S.low_ref(), S.low_batch(), F.FUSED, max_mems=4096)
+    S.assert_same(got, want)
+    assert got[3][:2] == [0, 0] and got[3][2] == int(sum(counts) > 4096)   # the first capacity of nine reads
+    got = F.seeds(S.low_ref(), S.low_batch(), F.FUSED)
+    S.assert_same(got, want)
+    assert got[3][:2] == [sum(c > S.MAX_MEMS_DEFAULT for c in counts), 0] and got[3][0] > 0
+
+
+@pytest.mark.parametrize("sa_intv,saved", [(1, False), (4, True), (7, False), (32, True)])
+def test_sampling_and_locate(gpu, tmp_path, host_sampled, sa_intv, saved):
+    """max_occ 3 samples the SMEMs with more occurrences (rows k, k + step, ..);
+    sa_intv 1 (the encoded rows come back and the host reads its suffix array),
+    4 and 32 from a saved and mapped index, 7 built in memory.  At the default
+    step cap no row of a sampled index is left to the host."""
+    path = tmp_path / "x.fcsidx" if saved else ""
+    got = F.seeds(S.plain_ref(), S.plain_batch()[:120], F.FUSED, sa_intv=sa_intv, index_path=path, **SAMPLED)
+    S.assert_same(got, host_sampled)
+    assert got[3][:2] == [0, 0]
+
+
+def test_step_cap_rows_are_repaired_on_the_host(gpu, host_sampled):
+    got = F.seeds(S.plain_ref(), S.plain_batch()[:120], F.FUSED, sa_intv=32, max_steps=3, **SAMPLED)
+    S.assert_same(got, host_sampled)
+    total = sum(len(x) for x in host_sampled[1])
+    assert got[3][0] == 0 and 0 < got[3][1] < total
+
+
+def test_capacity_retry_through_the_hook(gpu, host_plain):
+    got = F.seeds(S.plain_ref(), S.plain_batch(), F.FUSED, S.BWA, start_mem_cap=1, start_row_cap=1)
+    S.assert_same(got, host_plain[S.BWA])
+    assert got[3] == [0, 0, 1]
+
+
+def test_capacity_through_the_binding(gpu, host_plain, index8):
+    """Too small a capacity: FCS_FMD_SEED_MORE, the totals, and not one word of
+    mems / pos written; with exactly the totals: FCS_OK and the host's content."""
+    h, sa1 = index8
+    reads = S.plain_batch()
+    want = flat(host_plain[S.BWA][0], sa1)
+    tm, tr = int(want[1][-1]), int(want[3][-1])
+    assert tm > 100 and tr >= tm
+    for mem_cap, row_cap in ((tm - 1, tr), (tm, tr - 1), (0, 0), (1, 1)):
+        mems = np.zeros(tm, fcship.FMD_MEM)
+        mems.view(np.uint8)[:] = 0x5A   # a sentinel in every byte
+        pos = np.full(tr, -77, np.int64)
+        got = fcship.fmd_seed(h, *S.soa(reads), mem_cap=mem_cap, row_cap=row_cap, mems=mems, pos=pos)
+        assert got[5] == fcship.FCS_FMD_SEED_MORE
+        assert np.array_equal(got[1], want[1]) and np.array_equal(got[3], want[3]) and not got[4].any()
+        assert (mems.view(np.uint8) == 0x5A).all() and (pos == -77).all()
+    got = fcship.fmd_seed(h, *S.soa(reads), mem_cap=tm, row_cap=tr)
+    assert got[5] == fcship.FCS_OK
+    assert_flat(got, want)
+
+
+def test_empty_batch(gpu, index8):
+    h, _ = index8
+    e = np.zeros(0, np.uint8), np.zeros(0, np.int64), np.zeros(0, np.int32)
+    mems, mem_off, pos, row_off, overflow, status = fcship.fmd_seed(h, *e)
+    assert status == fcship.FCS_OK and list(mem_off) == [0] and list(row_off) == [0]
+    assert len(mems) == 0 and len(pos) == 0 and len(overflow) == 0
+
+
+def test_destroyed_handle_is_refused(gpu):
+    contigs = S.plain_ref()
+    occ, Carr, n_rows, sa, rows, ssa, flen = S.index_arrays(contigs, 8)
+    h = fcship.fmd_index_create(occ, Carr, n_rows, sa, 8, rows, ssa, flen)
+    assert fcship.fmd_seed(h, *S.soa(S.plain_batch()[:4]))[5] == fcship.FCS_OK
+    fcship.fmd_index_destroy(h)
+    with pytest.raises(fcship.FcsError) as e:   # the handle is gone: refused, not followed
+        fcship.fmd_seed(h, *S.soa(S.plain_batch()[:4]))
+    assert e.value.code == fcship.FCS_ERR_INVALID and "[E::fcs_fmd_seed]" in str(e.value)
+
+
+def test_four_threads_share_one_index(gpu, host_plain, index8):
+    """Four host threads, each with its own chunk and its own output buffers, on
+    one device and one index handle, three rounds: each chunk's result equals
+    the serial call's, which is the host's."""
+    h, sa1 = index8
+    reads = S.plain_batch()
+    chunks = [reads[k::4] for k in range(4)]
+
+    def work(chunk):
+        return fcship.fmd_seed(h, *S.soa(chunk))
+    serial = [work(c) for c in chunks]
+    for k in range(4):
+        assert serial[k][5] == fcship.FCS_OK and not serial[k][4].any()
+        assert_flat(serial[k], flat(host_plain[S.BWA][0][k::4], sa1))
+    out, errors = [None] * 4, []
+
+    def run(k):
+        try:
+            for _ in range(3):
+                out[k] = work(chunks[k])
+        except Exception as e:  # noqa: BLE001
+            errors.append(e)
+    threads = [threading.Thread(target=run, args=(k,)) for k in range(4)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    for k in range(4):
+        for a, b in zip(out[k], serial[k]):
+            assert np.array_equal(a, b)
+
+
+def align(tmp_path, name, key, fused, ref, *fastqs):
+    out = tmp_path / f"{name}_{key}_{fused}.bam"
+    args = ["align", "-r", ref, "-1", fastqs[0]] + (["-2", fastqs[1]] if len(fastqs) > 1 else []) + ["-o", out]
+    p = H.run_cli(*args, env={**ENV, "FCS_BWA_GPU_SEED": key, "FCS_BWA_GPU_SEED_FUSED": fused,
+                              "FCS_BWA_CHUNK_SIZE": "3000"}, cwd=tmp_path)
+    assert p.returncode == 0, p.stderr[-3000:]
+    return p.stderr, open(out, "rb").read(), open(str(out) + ".bai", "rb").read()
+
+
+def test_align_is_byte_identical_fused(gpu, tmp_path):
+    """`fcs-genome align` on the two data sets of test_fmd_seed_gpu.py (single
+    reads on a full suffix array; pairs on a saved index with sa_intv 8),
+    several chunks each: BAM and BAI of the fused path are those of the
+    two-call path and of the host's, and the log says which one ran."""
+    d = tmp_path / "se"
+    p = H.run_cli("synth", "-o", d, "-c", "chr20:150000,chr21:60000", "-x", "6", "--seed", "11", env=ENV, cwd=tmp_path)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d2 = tmp_path / "pe"
+    p = H.run_cli("synth", "-o", d2, "-c", "chr1:150000", "-x", "6", "--paired", "350", "--seed", "77", env=ENV,
+                  cwd=tmp_path)
+    assert p.returncode == 0, p.stderr[-2000:]
+    p = H.run_cli("index", "-r", d2 / "ref.fasta", "--sa-intv", "8", env=ENV, cwd=tmp_path)
+    assert p.returncode == 0, p.stderr[-2000:]
+    for name, ref, fq in (("se", d / "ref.fasta", [d / "sample.fastq"]),
+                          ("pe", d2 / "ref.fasta", [d2 / "sample_1.fastq", d2 / "sample_2.fastq"])):
+        log_fused, bam_fused, bai_fused = align(tmp_path, name, "true", "true", ref, *fq)
+        log_two, bam_two, bai_two = align(tmp_path, name, "true", "false", ref, *fq)
+        log_off, bam_off, bai_off = align(tmp_path, name, "false", "true", ref, *fq)
+        assert len(bam_fused) > 100000, name
+        assert bam_fused == bam_two and bai_fused == bai_two, name
+        assert bam_fused == bam_off and bai_fused == bai_off, name
+        expr = (r"GPU seeding \(bwa.gpu_seed\): (\d+) reads through the device, (\d+) of them collected on the "
+                r"host .*, (\d+) rows located on the host; seeding thread-seconds: collect ([\d.e-]+), locate "
+                r"([\d.e-]+), chain ([\d.e-]+)")
+        m, m2 = re.search(expr, log_fused), re.search(expr, log_two)
+        assert m and m2, log_fused[-3000:]
+        assert "fused" in m.group(0) and "fused" not in log_two and "GPU seeding" not in log_off
+        reads = int(re.search(r"(\d+) reads, ", log_fused).group(1))
+        assert int(m.group(1)) == reads and int(m.group(2)) == int(m2.group(2)) <= reads // 100
+        for log in (log_fused, log_two, log_off):   # the line the benchmark parses is as it was
+            assert re.search(r"alignment thread-seconds [\d.]+: seeding [\d.]+, extension [\d.]+, pairing [\d.]+, "
+                             r"records [\d.]+", log)

@@ -10,6 +10,10 @@ under `timeout`, alternated --rounds times on the same box:
         inputs resident, --kernel-reps launches per window), fcs_fmd_collect from and to host buffers (the
         synchronous call with its copies and the final sort); then the same
         two figures for fcs_fmd_locate over the rows the aligner samples;
+        then the fused pipeline on the same reads: fcs_fmd_seed_dev between
+        two events (collect, order, scan, expand, locate; inputs resident) and
+        the synchronous fcs_fmd_seed, beside the two-call sum (collect call +
+        row build + locate call) and the bytes each path copies back per read;
   host  FmdIndex::collect and FmdIndex::locate on --threads threads
         (fcsg_fmd_host_rates: parallel_for over the reads, as align_batch).
 Prints one JSON line per sa_intv: reads/s of collect and rows/s of locate
@@ -115,12 +119,14 @@ def leg_gpu(a):
     mems, n_mems, overflow = fcship.fmd_collect(h, codes, q_off, q_len, *BWA[:3], BWA[3], a.max_mems)
     collect_call_s = time.perf_counter() - t0
     # the rows seed_read samples from each SMEM
+    t0 = time.perf_counter()
     used = np.arange(a.max_mems)[None, :] < n_mems[:, None]
     k, s = mems["k"][used], mems["s"][used]
     step = np.where(s > MAX_OCC, s // MAX_OCC, 1)
     kept = np.minimum(s, MAX_OCC)
     r = np.repeat(k, kept) + (np.arange(kept.sum()) - np.repeat(np.cumsum(kept) - kept, kept)) * np.repeat(step, kept)
     r = r.astype(np.int64)
+    row_build_s = time.perf_counter() - t0
     with torch.cuda.stream(stream):
         d_rows = torch.from_numpy(r).to(dev)
         d_pos = torch.zeros(len(r), dtype=torch.int64, device=dev)
@@ -133,8 +139,34 @@ def leg_gpu(a):
     t0 = time.perf_counter()
     fcship.fmd_locate(h, r)
     locate_call_s = time.perf_counter() - t0
+    # the fused pipeline: the aligner's first capacities
+    mem_cap, row_cap = max(16 * n, 4096), max(64 * n, 65536)
+    SP = fcship.FmdSeedParams(P, MAX_OCC, 0)
+    with torch.cuda.stream(stream):
+        ws = torch.zeros(fcship.lib.fcs_fmd_seed_workspace_bytes(n, max_len, a.max_mems, row_cap), dtype=torch.uint8,
+                         device=dev)
+        f_mems = torch.zeros(mem_cap * 32, dtype=torch.uint8, device=dev)
+        f_pos = torch.zeros(row_cap, dtype=torch.int64, device=dev)
+        f_moff, f_roff = (torch.zeros(n + 1, dtype=torch.int64, device=dev) for _ in range(2))
+        fused_kernel_s = timed(lambda: fcship.check(fcship.lib.fcs_fmd_seed_dev(
+            h, d_codes.data_ptr(), len(codes), d_off.data_ptr(), d_len.data_ptr(), d_order.data_ptr(), n, max_len,
+            C.addressof(SP), ws.data_ptr(), ws.numel(), f_mems.data_ptr(), mem_cap, f_moff.data_ptr(), f_pos.data_ptr(),
+            row_cap, f_roff.data_ptr(), d_ov.data_ptr(), C.c_void_p(stream.cuda_stream))), a.kernel_reps)
+        fused_totals = [int(f_moff[-1].item()), int(f_roff[-1].item())]
+        fused_unlocated = int((f_pos[:fused_totals[1]] < 0).sum().item())
+    seed_args = (h, codes, q_off, q_len, *BWA[:3], BWA[3], a.max_mems, MAX_OCC)
+    fcship.fmd_seed(*seed_args)
+    t0 = time.perf_counter()
+    f = fcship.fmd_seed(*seed_args)
+    fused_call_s = time.perf_counter() - t0
+    assert f[5] == fcship.FCS_OK and fused_totals == [int(f[1][-1]), int(f[3][-1])] == [int(n_mems.sum()), len(r)]
     fcship.fmd_index_destroy(h)
-    return {"reads": n, "smems": int(n_mems.sum()), "overflow_reads": int(overflow.sum()), "rows": len(r),
+    return {"fused_kernel_s": fused_kernel_s, "fused_call_s": fused_call_s, "row_build_s": row_build_s,
+            "two_call_s": collect_call_s + row_build_s + locate_call_s,
+            "two_kernels_s": collect_kernel_s + locate_kernel_s, "fused_unlocated_rows": fused_unlocated,
+            "d2h_bytes_per_read": {"two_call": 8 + 32 * a.max_mems + 12 * len(r) / n,
+                                   "fused": 20 + (32 * int(n_mems.sum()) + 8 * len(r)) / n},
+            "reads": n, "smems": int(n_mems.sum()), "overflow_reads": int(overflow.sum()), "rows": len(r),
             "rows_past_step_cap": capped, "collect_kernel_s": collect_kernel_s, "collect_call_s": collect_call_s,
             "locate_kernel_s": locate_kernel_s, "locate_call_s": locate_call_s}
 
@@ -204,6 +236,12 @@ def main():
             "collect_reads_per_s": {"gpu_kernel": rate("gpu", "collect_kernel_s", g["reads"]),
                                     "gpu_sync_call": rate("gpu", "collect_call_s", g["reads"]),
                                     f"host_{a.threads}t": rate("host", "collect_s", h["reads"])},
+            "fused_reads_per_s": {"gpu_kernels": rate("gpu", "fused_kernel_s", g["reads"]),
+                                  "collect_plus_locate_kernels": rate("gpu", "two_kernels_s", g["reads"]),
+                                  "gpu_sync_call": rate("gpu", "fused_call_s", g["reads"]),
+                                  "two_call_sum": rate("gpu", "two_call_s", g["reads"])},
+            "d2h_bytes_per_read": {k: round(v, 1) for k, v in g["d2h_bytes_per_read"].items()},
+            "fused_unlocated_rows": g["fused_unlocated_rows"],
             "locate_rows_per_s": {"gpu_kernel": rate("gpu", "locate_kernel_s", g["rows"]),
                                   "gpu_sync_call": rate("gpu", "locate_call_s", g["rows"]),
                                   f"host_{a.threads}t": rate("host", "locate_s", h["rows"])},
