@@ -479,6 +479,28 @@ int get_device_tables(int device, DeviceTables** out) {
   return FCS_OK;
 }
 
+int device_ok(int device) { return check_device(device); }
+
+int call_session_acquire(int device, size_t host_bytes, size_t dev_bytes, CallSession& c) {
+  auto lease = std::make_unique<SessionLease>();
+  int rc = lease->acquire(device);
+  if (rc) return rc;
+  Session* S = lease->get();
+  if ((rc = S->ensure_host(host_bytes)) || (rc = S->ensure_dev(dev_bytes))) return rc;
+  c.s = S->s;
+  c.host = static_cast<char*>(S->host);
+  c.dev = static_cast<char*>(S->dev);
+  c.lease = lease.release();
+  return FCS_OK;
+}
+
+void call_session_release(CallSession& c) {
+  if (!c.lease) return;
+  (void)hipStreamSynchronize(c.s);  // StreamDrain's reason: the next holder refills the pinned staging
+  delete static_cast<SessionLease*>(c.lease);
+  c = CallSession();
+}
+
 }  // namespace fcs
 
 using namespace fcs;

@@ -310,4 +310,34 @@ int launch_fmd_seed(const FmdDevIndex& dx, const FmdIv* slots, int32_t max_mems,
                     int32_t* n_eff, int64_t* n_rows, int64_t* mem_off, int64_t* row_off, FmdIv* mems, int64_t mem_cap,
                     int64_t* rows, int64_t* pos, int64_t row_cap, hipStream_t s);
 
+// ------------------------------------------------------------ call sessions
+// A pooled compute session (fcship_api.cpp) leased for one synchronous call of
+// an entry point that lives in another file (markdup.hip): its stream and its
+// pinned host and device arenas, grown to the sizes asked for.  The release
+// synchronises the stream before the session goes back to the pool.
+struct CallSession {
+  hipStream_t s = nullptr;
+  char* host = nullptr;
+  char* dev = nullptr;
+  void* lease = nullptr;
+};
+int call_session_acquire(int device, size_t host_bytes, size_t dev_bytes, CallSession& c);
+void call_session_release(CallSession& c);
+// FCS_OK when `device` is a visible ordinal (FCS_ERR_DEVICE without any device).
+int device_ok(int device);
+
+// ------------------------------------------------------------ duplicate marking
+// Device view of an fcsdup_batch (include/fcsdup.h), markdup.hip.
+struct MdDevBatch {
+  int64_t n;
+  const uint16_t* flag;
+  const int32_t *ref_id, *pos, *mate, *lib;
+  const uint32_t* cigar;
+  const int64_t* cigar_off;
+  int64_t n_cigar;
+  const uint8_t* qual;
+  const int64_t* qual_off;
+  int64_t n_qual;
+};
+
 }  // namespace fcs

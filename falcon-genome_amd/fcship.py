@@ -721,3 +721,61 @@ def fmd_seed(handle, codes, q_off, q_len, min_len=19, split_len=28, split_width=
         return mems, mem_off, pos, row_off, overflow[:n], rc
     check(rc)
     return mems[:mem_off[-1]], mem_off, pos[:row_off[-1]], row_off, overflow[:n], rc
+
+
+# ---------------------------------------------------------------- duplicate marking (include/fcsdup.h)
+DUP_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "fcsdup.h")
+FCSDUP_MAX_REFS, FCSDUP_MAX_LIBS, FCSDUP_MAX_POS = (1 << 21) - 1, (1 << 11) - 1, 1 << 30
+FCSDUP_STATUS_POS, FCSDUP_STATUS_FIELD = 1, 2
+
+
+class DupBatch(C.Structure):
+    _fields_ = [("n", C.c_int64), ("flag", C.c_void_p), ("ref_id", C.c_void_p), ("pos", C.c_void_p),
+                ("mate", C.c_void_p), ("lib", C.c_void_p), ("cigar", C.c_void_p), ("cigar_off", C.c_void_p),
+                ("n_cigar", C.c_int64), ("qual", C.c_void_p), ("qual_off", C.c_void_p), ("n_qual", C.c_int64),
+                ("n_ref", C.c_int32), ("n_lib", C.c_int32)]
+
+
+class DupStats(C.Structure):
+    _fields_ = [("examined", C.c_int64), ("pairs", C.c_int64), ("fragments", C.c_int64), ("duplicates", C.c_int64)]
+
+
+_sig("fcsdup_mark", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
+_sig("fcsdup_workspace_bytes", C.c_int64, [C.c_int64])
+_sig("fcsdup_mark_dev", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p])
+
+
+def dup_header_symbols() -> list[str]:
+    """Function names declared in include/fcsdup.h."""
+    import re
+    txt = re.sub(r"/\*.*?\*/", "", open(DUP_HEADER_PATH).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(fcsdup_[a-z0-9_]+)\s*\(", txt)))
+
+
+def dup_arrays(flag, ref_id, pos, mate, lib, cigar, cigar_off, qual, qual_off):
+    """The batch's arrays in the dtypes fcsdup_batch names."""
+    return (np.ascontiguousarray(flag, np.uint16), np.ascontiguousarray(ref_id, np.int32),
+            np.ascontiguousarray(pos, np.int32), np.ascontiguousarray(mate, np.int32),
+            np.ascontiguousarray(lib, np.int32), np.ascontiguousarray(cigar, np.uint32),
+            np.ascontiguousarray(cigar_off, np.int64), np.ascontiguousarray(qual, np.uint8),
+            np.ascontiguousarray(qual_off, np.int64))
+
+
+def dup_batch(arrays, n_ref: int, n_lib: int, n=None, n_cigar=None, n_qual=None) -> DupBatch:
+    """fcsdup_batch over host arrays (dup_arrays' tuple, which the caller keeps alive)."""
+    flag, ref_id, pos, mate, lib, cigar, cigar_off, qual, qual_off = arrays
+    return DupBatch(len(flag) if n is None else n, _ptr(flag), _ptr(ref_id), _ptr(pos), _ptr(mate), _ptr(lib),
+                    _ptr(cigar), _ptr(cigar_off), len(cigar) if n_cigar is None else n_cigar, _ptr(qual),
+                    _ptr(qual_off), len(qual) if n_qual is None else n_qual, n_ref, n_lib)
+
+
+def dup_mark(arrays, n_ref: int, n_lib: int, device: int = 0, **kw):
+    """fcsdup_mark: (dup[n] uint8, {examined, pairs, fragments, duplicates})."""
+    arrays = dup_arrays(*arrays)
+    b = dup_batch(arrays, n_ref, n_lib, **kw)
+    dup = np.full(max(len(arrays[0]), 1), 0xEE, np.uint8)
+    st = DupStats(-1, -1, -1, -1)
+    check(lib.fcsdup_mark(device, C.addressof(b), dup.ctypes.data, C.addressof(st)))
+    return dup[:len(arrays[0])], dict(examined=st.examined, pairs=st.pairs, fragments=st.fragments,
+                                      duplicates=st.duplicates)

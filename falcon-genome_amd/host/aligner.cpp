@@ -24,6 +24,7 @@
 #include "executor.h"
 #include "fcship.h"
 #include "intervals.h"
+#include "markdup.h"
 #include "seedext.h"
 #include "workers.h"
 
@@ -1675,6 +1676,17 @@ AlignStats align_fastq(const AlignJob& job, const std::vector<int>& devices, std
       std::vector<BamRecord>().swap(v);
     }
   }
+  // markdup.in_align: the read group's records are one batch (host/markdup.h),
+  // marked before the sort, so the merged BAM and the bucket BAMs carry the same flags
+  const bool mark = !job.align_only && conf().get_bool("markdup.in_align");
+  MarkdupStats md;
+  if (mark) {
+    int md_device = -1;
+    if (conf().get_bool("markdup.gpu"))
+      for (int d : devices)
+        if (d >= 0 && md_device < 0) md_device = d;
+    md = mark_duplicates(recs, std::vector<int32_t>(recs.size(), 0), 1, (int32_t)ref.contigs.size(), md_device);
+  }
   const uint64_t t_aln = now_us();
   // coordinate order by packed keys (reference id as unsigned: unmapped last;
   // the position's sign bit flipped; ties by input order, as a stable sort)
@@ -1767,6 +1779,10 @@ AlignStats align_fastq(const AlignJob& job, const std::vector<int>& devices, std
         << "), " << tot.seed_host_rows << " rows located on the host; seeding thread-seconds: collect "
         << tot.seed_collect_seconds << ", locate " << tot.seed_locate_seconds << ", chain " << tot.seed_chain_seconds
         << "\n";
+  if (mark)
+    rep << "[fcs-genome align] mark duplicates: " << md.examined << " records examined, " << md.pairs << " pairs, "
+        << md.fragments << " fragments, " << md.duplicates << " records flagged, " << md.seconds << " s ("
+        << (md.on_device ? "GPU" : "host") << ")\n";
   report = rep.str();
   return tot;
 }

@@ -149,6 +149,7 @@ struct AlignJob {
   std::string rg = "sample", sample = "sample", platform = "illumina", library = "sample";
   int bgzf_device = -1;        // >= 0: the BAM's blocks compress on that GPU (gpu.bgzf_deflate)
   bool disable_merge = false;  // bwa.num_buckets sorted bucket BAMs (+ .bai, .bed) in the directory `output`
+  bool align_only = false;     // --align-only: no duplicate marking even with markdup.in_align
 };
 
 // Aligns one read group on the device slots `gpus`: FASTQ chunks

@@ -21,6 +21,7 @@
 #include "seedext.h"
 #include "aligner.h"
 #include "intervals.h"
+#include "markdup.h"
 #include "sample_sheet.h"
 #include "vcf.h"
 
@@ -479,6 +480,23 @@ int fcsg_text_to_bam(const char* text, const char* bam, const char* names_csv, c
       w.write(r);
     }
     w.close();
+  });
+}
+
+// mark_duplicates_host over a flat batch (the layout of include/fcsdup.h):
+// dup[n] and stats = {examined, pairs, fragments, duplicate records}.
+int fcsg_markdup(int64_t n, const uint16_t* flag, const int32_t* ref_id, const int32_t* pos, const int32_t* mate,
+                 const int32_t* lib, const uint32_t* cigar, const int64_t* cigar_off, const uint8_t* qual,
+                 const int64_t* qual_off, int32_t n_ref, int32_t n_lib, uint8_t* dup, int64_t* stats) {
+  return guard([&] {
+    fcsdup_batch b;
+    b.n = n;
+    b.flag = flag, b.ref_id = ref_id, b.pos = pos, b.mate = mate, b.lib = lib;
+    b.cigar = cigar, b.cigar_off = cigar_off, b.n_cigar = n > 0 ? cigar_off[n] : 0;
+    b.qual = qual, b.qual_off = qual_off, b.n_qual = n > 0 ? qual_off[n] : 0;
+    b.n_ref = n_ref, b.n_lib = n_lib;
+    const MarkdupStats st = mark_duplicates_host(b, dup);
+    stats[0] = st.examined, stats[1] = st.pairs, stats[2] = st.fragments, stats[3] = st.duplicates;
   });
 }
 

@@ -60,6 +60,10 @@ void Config::init(const std::string& root_dir) {
           "inflate a calling window's BAM blocks on the GPU (fcs_bgzf_inflate) instead of host libdeflate");
   declare("gpu.bgzf_deflate", "false",
           "compress the final VCF.gz's and align's BAM blocks on the GPU (fcs_bgzf_deflate) instead of host libdeflate");
+  declare("markdup.in_align", "false",
+          "align marks duplicates in each read group before the coordinate sort (unless --align-only)");
+  declare("markdup.gpu", "false",
+          "mark duplicates on the GPU (fcsdup_mark) instead of on the host (markdup, and align with markdup.in_align)");
   // caller knobs (GATK HaplotypeCaller / Mutect2 argument defaults)
   declare("htc.min_base_quality", "10", "min base quality counted as evidence of activity");
   declare("htc.base_quality_threshold", "18", "PairHMM: base quals below this become 6");

@@ -28,6 +28,7 @@
 #include "fcship.h"
 #include "aligner.h"
 #include "intervals.h"
+#include "markdup.h"
 #include "sample_sheet.h"
 #include "synth.h"
 #include "workers.h"
@@ -331,7 +332,7 @@ int align_main(int argc, char** argv) {
   a.add("sp", "S", false, false, "sample id ('SM' in BAM header)");
   a.add("pl", "P", false, false, "platform id ('PL' in BAM header)");
   a.add("lb", "L", false, false, "library id ('LB' in BAM header)");
-  a.add("align-only", "l", true, false, "skip mark duplicates");
+  a.add("align-only", "l", true, false, "skip mark duplicates (they are marked only with markdup.in_align=true)");
   a.add("disable-merge", "", true, false, "give bucket bams instead of the whole bam");
   try {
     a.parse(argc, argv);
@@ -341,7 +342,7 @@ int align_main(int argc, char** argv) {
   }
   const std::string ref = a.get("ref"), sheet = a.get("sample_sheet"), fq1 = a.get("fastq1"), fq2 = a.get("fastq2");
   const std::string output = a.get("output");
-  const bool force = a.has("force"), disable_merge = a.has("disable-merge");
+  const bool force = a.has("force"), disable_merge = a.has("disable-merge"), align_only = a.has("align-only");
   const std::vector<std::string> extra = a.all("extra-options");
   SampleSheetMap samples;
   if (sheet.empty()) {
@@ -386,7 +387,8 @@ int align_main(int argc, char** argv) {
                            " more than once (each read group is aligned to its own BAM)");
       rg_out.push_back(out_rg);
       ex.addTask(std::make_shared<BWAWorker>(ref, d.fastqR1, d.fastqR2, out_rg, extra, sample_id, d.ReadGroup,
-                                             d.Platform, d.LibraryID, !disable_merge, force || list.size() > 1, gpus),
+                                             d.Platform, d.LibraryID, !disable_merge, force || list.size() > 1, gpus,
+                                             align_only),
                  sample_id, true);
     }
     if (list.size() > 1) {
@@ -405,6 +407,36 @@ int align_main(int argc, char** argv) {
     }
     ex.run();
   }
+  return 0;
+}
+
+// `fcs-genome markdup -i in.bam -o out.bam` (reference src/worker-markdup.cpp,
+// which runs sambamba markdup): the whole BAM is read into memory, marked as
+// one batch (host/markdup.h) and written in its input order.  With
+// markdup.gpu=false the command needs no GPU.
+int markdup_main(int argc, char** argv) {
+  Args a;
+  common_opts(a);
+  a.add("input", "i", false, true, "input BAM file");
+  a.add("output", "o", false, true, "output BAM file (a .bai is written when the input is coordinate-sorted)");
+  try {
+    a.parse(argc, argv);
+  } catch (helpRequest&) {
+    std::cerr << "'fcs-genome markdup' options:\n"
+              << a.help()
+              << "The input is held in memory as a whole (about 2.5x its uncompressed size); "
+                 "there is no spilling, out-of-core mode.\n";
+    throw;
+  }
+  const std::string input = a.get("input"), output = a.get("output");
+  if (!is_regular_file(input)) throw fileNotFound(input);
+  if (!a.has("force") && path_exists(output)) throw invalidParam("output " + output + " exists (use -f)");
+  int device = -1;
+  if (conf().get_bool("markdup.gpu")) device = slots().front();
+  const MarkdupStats st = markdup_bam(input, output, device);
+  std::cerr << "[fcs-genome markdup] " << st.examined << " records examined, " << st.pairs << " pairs, " << st.fragments
+            << " fragments, " << st.duplicates << " records flagged, " << st.seconds << " s ("
+            << (st.on_device ? "GPU" : "host") << ")" << std::endl;
   return 0;
 }
 
@@ -535,6 +567,7 @@ int print_help() {
   std::cout << "Falcon Genome Analysis Toolkit (MI355X / gfx950 build)\n"
                "Usage: fcs-genome [command] <options>\n\nCommands:\n"
                "  align           align FASTQ reads into a sorted BAM (GPU banded SW)\n"
+               "  markdup         mark duplicate reads of a BAM (GPU sort + segmented arg-max)\n"
                "  htc             variant calling, HaplotypeCaller-style (GPU PairHMM)\n"
                "  mutect2         somatic variant calling, tumor/normal (GPU PairHMM)\n"
                "  conf            print configuration keys\n"
@@ -574,6 +607,7 @@ int main(int argc, char** argv) {
     if (cmd == "htc") ret = htc_main(argc - 1, argv + 1);
     else if (cmd == "mutect2") ret = mutect2_main(argc - 1, argv + 1);
     else if (cmd == "align" || cmd == "al") ret = align_main(argc - 1, argv + 1);
+    else if (cmd == "markdup" || cmd == "md") ret = markdup_main(argc - 1, argv + 1);
     else if (cmd == "synth") ret = synth_main(argc - 1, argv + 1);
     else if (cmd == "index") ret = index_main(argc - 1, argv + 1);
     else if (cmd == "conf") {

@@ -224,7 +224,7 @@ int TabixWorker::run(TaskContext&) {
 BWAWorker::BWAWorker(std::string ref_path, std::string fq1_path, std::string fq2_path, std::string output_path,
                      std::vector<std::string> extra_opts, std::string sample_id, std::string read_group,
                      std::string platform_id, std::string library_id, bool flag_merge_bams, bool flag_f,
-                     std::vector<int> gpus)
+                     std::vector<int> gpus, bool flag_align_only)
     : Worker(1, 1, std::move(extra_opts), "bwa mem"),
       ref_path_(std::move(ref_path)),
       fq1_path_(std::move(fq1_path)),
@@ -236,6 +236,7 @@ BWAWorker::BWAWorker(std::string ref_path, std::string fq1_path, std::string fq2
       library_id_(std::move(library_id)),
       flag_merge_bams_(flag_merge_bams),
       flag_f_(flag_f),
+      flag_align_only_(flag_align_only),
       gpus_(std::move(gpus)) {}
 
 void BWAWorker::check() {
@@ -270,6 +271,7 @@ int BWAWorker::run(TaskContext& ctx) {
   job.platform = platform_id_;
   job.library = library_id_;
   job.disable_merge = !flag_merge_bams_;
+  job.align_only = flag_align_only_;
   if (conf().get_bool("gpu.bgzf_deflate"))
     for (int d : gpus_)
       if (d >= 0 && job.bgzf_device < 0) job.bgzf_device = d;

@@ -110,13 +110,13 @@ class BWAWorker : public Worker {
   BWAWorker(std::string ref_path, std::string fq1_path, std::string fq2_path, std::string output_path,
             std::vector<std::string> extra_opts, std::string sample_id, std::string read_group,
             std::string platform_id, std::string library_id, bool flag_merge_bams, bool flag_f,
-            std::vector<int> gpus);
+            std::vector<int> gpus, bool flag_align_only = false);
   void check() override;
   int run(TaskContext& ctx) override;
 
  private:
   std::string ref_path_, fq1_path_, fq2_path_, output_path_, sample_id_, read_group_, platform_id_, library_id_;
-  bool flag_merge_bams_, flag_f_;
+  bool flag_merge_bams_, flag_f_, flag_align_only_ = false;
   std::vector<int> gpus_;
 };
 
