@@ -779,3 +779,98 @@ def dup_mark(arrays, n_ref: int, n_lib: int, device: int = 0, **kw):
     check(lib.fcsdup_mark(device, C.addressof(b), dup.ctypes.data, C.addressof(st)))
     return dup[:len(arrays[0])], dict(examined=st.examined, pairs=st.pairs, fragments=st.fragments,
                                       duplicates=st.duplicates)
+
+
+# ---------------------------------------------------------------- base quality recalibration (include/fcsbq.h)
+BQ_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "fcsbq.h")
+FCSBQ_NQ, FCSBQ_NCTX, FCSBQ_NCYC, FCSBQ_MAX_CYCLE, FCSBQ_MAX_RG = 94, 16, 1000, 500, 1024
+FCSBQ_STATUS_FIELD, FCSBQ_STATUS_REF, FCSBQ_STATUS_LONG = 1, 2, 4
+
+
+class BqBatch(C.Structure):
+    _fields_ = [("n", C.c_int64), ("flag", C.c_void_p), ("ref_id", C.c_void_p), ("pos", C.c_void_p),
+                ("mapq", C.c_void_p), ("rg", C.c_void_p), ("cigar", C.c_void_p), ("cigar_off", C.c_void_p),
+                ("n_cigar", C.c_int64), ("bases", C.c_void_p), ("qual", C.c_void_p), ("base_off", C.c_void_p),
+                ("n_bases", C.c_int64), ("qual_absent", C.c_void_p)]
+
+
+_sig("fcsbq_ref_create", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)])
+_sig("fcsbq_ref_destroy", C.c_int, [C.c_void_p])
+_sig("fcsbq_count", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p])
+_sig("fcsbq_apply", C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+_sig("fcsbq_workspace_bytes", C.c_int64, [C.c_int32])
+_sig("fcsbq_count_dev", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p])
+_sig("fcsbq_apply_dev", C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p])
+
+
+def bq_header_symbols() -> list[str]:
+    """Function names declared in include/fcsbq.h."""
+    import re
+    txt = re.sub(r"/\*.*?\*/", "", open(BQ_HEADER_PATH).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(fcsbq_[a-z0-9_]+)\s*\(", txt)))
+
+
+_BQ_DTYPES = (np.uint16, np.int32, np.int32, np.uint8, np.int32, np.uint32, np.int64, np.uint8, np.uint8, np.int64,
+              np.uint8)
+
+
+def bq_arrays(flag, ref_id, pos, mapq, rg, cigar, cigar_off, bases, qual, base_off, qual_absent):
+    """The batch's arrays in the dtypes fcsbq_batch names."""
+    return tuple(np.ascontiguousarray(a, t) for a, t in zip(
+        (flag, ref_id, pos, mapq, rg, cigar, cigar_off, bases, qual, base_off, qual_absent), _BQ_DTYPES))
+
+
+def bq_batch(arrays, n=None, n_cigar=None, n_bases=None) -> BqBatch:
+    """fcsbq_batch over host arrays (bq_arrays' tuple, which the caller keeps alive)."""
+    flag, ref_id, pos, mapq, rg, cigar, cigar_off, bases, qual, base_off, absent = arrays
+    return BqBatch(len(flag) if n is None else n, _ptr(flag), _ptr(ref_id), _ptr(pos), _ptr(mapq), _ptr(rg), _ptr(cigar),
+                   _ptr(cigar_off), len(cigar) if n_cigar is None else n_cigar, _ptr(bases), _ptr(qual), _ptr(base_off),
+                   len(bases) if n_bases is None else n_bases, _ptr(absent))
+
+
+class bq_ref:
+    """fcsbq_ref_create / destroy: a device copy of the reference and its known-sites bitmap."""
+
+    def __init__(self, bases, ref_off, known_bits, device: int = 0):
+        bases = np.ascontiguousarray(bases, np.uint8)
+        ref_off = np.ascontiguousarray(ref_off, np.int64)
+        known_bits = np.ascontiguousarray(known_bits, np.uint64)
+        assert len(known_bits) >= (int(ref_off[-1]) + 63) // 64
+        self.handle = C.c_void_p()
+        check(lib.fcsbq_ref_create(device, bases.ctypes.data, ref_off.ctypes.data, len(ref_off) - 1,
+                                   known_bits.ctypes.data, C.byref(self.handle)))
+
+    def close(self):
+        if self.handle:
+            check(lib.fcsbq_ref_destroy(self.handle))
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def bq_count(ref: "bq_ref", arrays, n_rg: int, ctx=None, cyc=None, **kw):
+    """fcsbq_count: the batch's counts added to ctx[n_rg, 94, 16, 2] and cyc[n_rg, 94, 1000, 2] (new when None)."""
+    arrays = bq_arrays(*arrays)
+    b = bq_batch(arrays, **kw)
+    ctx = np.zeros((n_rg, FCSBQ_NQ, FCSBQ_NCTX, 2), np.int64) if ctx is None else ctx
+    cyc = np.zeros((n_rg, FCSBQ_NQ, FCSBQ_NCYC, 2), np.int64) if cyc is None else cyc
+    assert ctx.dtype == np.int64 and cyc.dtype == np.int64 and ctx.flags.c_contiguous and cyc.flags.c_contiguous
+    check(lib.fcsbq_count(ref.handle, C.addressof(b), n_rg, ctx.ctypes.data, cyc.ctypes.data))
+    return ctx, cyc
+
+
+def bq_apply(arrays, base, dctx, dcyc, device: int = 0, out=None, **kw):
+    """fcsbq_apply: the new quality bytes in the batch's layout."""
+    arrays = bq_arrays(*arrays)
+    b = bq_batch(arrays, **kw)
+    base, dctx, dcyc = (np.ascontiguousarray(a, np.float64) for a in (base, dctx, dcyc))
+    out = np.full(max(len(arrays[7]), 1), 0xEE, np.uint8) if out is None else out
+    check(lib.fcsbq_apply(device, C.addressof(b), base.shape[0], base.ctypes.data, dctx.ctypes.data, dcyc.ctypes.data,
+                          out.ctypes.data))
+    return out[:len(arrays[7])]

@@ -1,0 +1,431 @@
+// The baserecal / printreads / bqsr commands (bqsr_run.h): the reference and
+// its known-sites bitmap, the streaming passes over the BAM in chunks of
+// bqsr.chunk_records, the flattening, and the device calls or the host rules.
+#include "bqsr_run.h"
+
+#include <dlfcn.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <mutex>
+#include <sstream>
+#include <unordered_map>
+
+#include "bam.h"
+#include "bgzf.h"
+#include "bqsr.h"
+#include "common.h"
+#include "config.h"
+#include "fasta.h"
+#include "fcship.h"
+#include "intervals.h"
+
+namespace fcsg {
+
+namespace {
+
+struct BqApi {
+  decltype(&fcsbq_ref_create) ref_create = nullptr;
+  decltype(&fcsbq_ref_destroy) ref_destroy = nullptr;
+  decltype(&fcsbq_count) count = nullptr;
+  decltype(&fcsbq_apply) apply = nullptr;
+  const char* (*last_error)() = nullptr;
+};
+
+const BqApi& bq_api() {
+  static const BqApi A = [] {
+    BqApi a;
+    a.ref_create = reinterpret_cast<decltype(a.ref_create)>(dlsym(RTLD_DEFAULT, "fcsbq_ref_create"));
+    a.ref_destroy = reinterpret_cast<decltype(a.ref_destroy)>(dlsym(RTLD_DEFAULT, "fcsbq_ref_destroy"));
+    a.count = reinterpret_cast<decltype(a.count)>(dlsym(RTLD_DEFAULT, "fcsbq_count"));
+    a.apply = reinterpret_cast<decltype(a.apply)>(dlsym(RTLD_DEFAULT, "fcsbq_apply"));
+    a.last_error = reinterpret_cast<decltype(a.last_error)>(dlsym(RTLD_DEFAULT, "fcs_last_error"));
+    return a;
+  }();
+  return A;
+}
+
+// The device the job runs on, or -1 (with one log line when the library lacks the entry points).
+int device_of(const BqsrJob& job) {
+  if (job.device < 0) return -1;
+  if (gpu_bqsr_available()) return job.device;
+  static std::once_flag said;
+  std::call_once(said, [] {
+    std::fprintf(stderr, "[fcs-genome bqsr] bqsr.gpu: the loaded libfcship has no fcsbq_count entry point; "
+                         "qualities are recalibrated on the host\n");
+  });
+  return -1;
+}
+
+int host_threads() { return (int)std::min<unsigned>(host_cpus(), 16); }
+
+// The input's BAM files: the file itself, or a directory's part BAMs in name order.
+std::vector<std::string> input_bams(const std::string& input) {
+  if (is_regular_file(input)) return {input};
+  if (!is_directory(input)) throw fileNotFound(input);
+  std::vector<std::string> names = list_dir(input, ".bam");
+  std::sort(names.begin(), names.end());
+  std::vector<std::string> out;
+  for (const std::string& n : names) out.push_back(n.find('/') == std::string::npos ? input + "/" + n : n);
+  if (out.empty()) throw fileNotFound(input + "/*.bam");
+  return out;
+}
+
+// The header's read groups: ids[k] the @RG ID, names[k] its PU when present, else the ID.
+void read_groups(const BamHeader& h, std::vector<std::string>& ids, std::vector<std::string>& names) {
+  std::istringstream ss(h.text);
+  for (std::string line; std::getline(ss, line);) {
+    if (line.rfind("@RG", 0) != 0) continue;
+    std::string id, pu;
+    for (size_t p = 0; p < line.size();) {
+      const size_t e = std::min(line.find('\t', p), line.size());
+      const std::string f = line.substr(p, e - p);
+      if (f.rfind("ID:", 0) == 0) id = f.substr(3);
+      if (f.rfind("PU:", 0) == 0) pu = f.substr(3);
+      p = e + 1;
+    }
+    if (id.empty()) continue;
+    ids.push_back(id);
+    names.push_back(pu.empty() ? id : pu);
+  }
+}
+
+// The reference in the BAM header's contig order, with the known-sites bitmap.
+struct BqGenome {
+  std::vector<uint8_t> bases;
+  std::vector<int64_t> ref_off;
+  std::vector<uint64_t> known;
+  BqRefView view() const {
+    BqRefView v;
+    v.bases = bases.data(), v.ref_off = ref_off.data(), v.n_ref = (int32_t)ref_off.size() - 1, v.known = known.data();
+    return v;
+  }
+};
+
+BqGenome load_genome(const std::string& fasta, const BamHeader& h) {
+  const Reference ref = load_fasta(fasta);
+  BqGenome g;
+  g.ref_off.assign(1, 0);
+  for (size_t k = 0; k < h.names.size(); ++k) {
+    const int c = ref.index(h.names[k]);
+    if (c < 0) throw invalidParam("contig " + h.names[k] + " of the BAM header is not in " + fasta);
+    const std::string& s = ref.contigs[(size_t)c].seq;
+    g.bases.insert(g.bases.end(), s.begin(), s.end());
+    g.ref_off.push_back((int64_t)g.bases.size());
+  }
+  g.known.assign((g.bases.size() + 63) / 64 + 1, 0);
+  return g;
+}
+
+// CHROM, POS and REF of every record of a plain or bgzipped VCF: the bits POS-1 .. POS-1+len(REF)-1.
+void load_known_sites(const std::string& path, const BamHeader& h, BqGenome& g, BqsrStats& st) {
+  if (!is_regular_file(path)) throw fileNotFound(path);
+  std::unordered_map<std::string, int> index;
+  for (size_t k = 0; k < h.names.size(); ++k) index[h.names[k]] = (int)k;
+  auto take = [&](const std::string& line) {
+    if (line.empty() || line[0] == '#') return;
+    const size_t t1 = line.find('\t');
+    const size_t t2 = t1 == std::string::npos ? t1 : line.find('\t', t1 + 1);
+    const size_t t3 = t2 == std::string::npos ? t2 : line.find('\t', t2 + 1);
+    const size_t t4 = t3 == std::string::npos ? t3 : line.find('\t', t3 + 1);
+    if (t3 == std::string::npos) throw formatError("known sites " + path + ": a record of fewer than 4 fields");
+    const auto it = index.find(line.substr(0, t1));
+    if (it == index.end()) {
+      ++st.known_skipped;
+      return;
+    }
+    int64_t pos;
+    try {
+      pos = std::stoll(line.substr(t1 + 1, t2 - t1 - 1));
+    } catch (const std::logic_error&) {
+      throw formatError("known sites " + path + ": POS of \"" + line.substr(0, std::min<size_t>(line.size(), 60)) + "\"");
+    }
+    const int64_t len = (int64_t)((t4 == std::string::npos ? line.size() : t4) - t3 - 1);
+    const int64_t g0 = g.ref_off[(size_t)it->second], clen = g.ref_off[(size_t)it->second + 1] - g0;
+    for (int64_t p = std::max<int64_t>(pos - 1, 0); p < pos - 1 + len && p < clen; ++p)
+      g.known[(size_t)((g0 + p) >> 6)] |= (uint64_t)1 << ((g0 + p) & 63);
+    ++st.known_sites;
+  };
+  std::string line;
+  if (is_bgzf_file(path)) {
+    BgzfReader in(path);
+    while (in.getline(line)) take(line);
+  } else {
+    std::ifstream in(path);
+    while (std::getline(in, line)) {
+      if (!line.empty() && line.back() == '\r') line.pop_back();
+      take(line);
+    }
+  }
+}
+
+// -L: the intervals by contig index, sorted; a record is kept when it overlaps one.
+struct Regions {
+  bool all = true;
+  std::vector<std::vector<std::pair<int64_t, int64_t>>> by_ref;  // 0-based half-open
+  bool keep(const BamRecord& r) const {
+    if (all) return true;
+    if (r.ref_id < 0 || (size_t)r.ref_id >= by_ref.size() || r.pos < 0) return false;
+    const int64_t beg = r.pos, end = std::max<int64_t>(r.end(), (int64_t)r.pos + 1);
+    for (const auto& iv : by_ref[(size_t)r.ref_id]) {
+      if (iv.first >= end) break;
+      if (iv.second > beg) return true;
+    }
+    return false;
+  }
+};
+
+Regions load_regions(const std::string& path, const BamHeader& h) {
+  Regions rg;
+  if (path.empty()) return rg;
+  if (!is_regular_file(path)) throw fileNotFound(path);
+  rg.all = false;
+  rg.by_ref.resize(h.names.size());
+  for (const Interval& iv : read_regions(path)) {
+    const int c = h.ref_index(iv.chrom);
+    if (c >= 0) rg.by_ref[(size_t)c].emplace_back(iv.lb - 1, iv.ub);
+  }
+  for (auto& v : rg.by_ref) std::sort(v.begin(), v.end());
+  return rg;
+}
+
+// One chunk of records as an fcsbq_batch over its own arrays, in the order `order`.
+struct FlatBatch {
+  std::vector<uint16_t> flag;
+  std::vector<int32_t> ref_id, pos, rg;
+  std::vector<uint8_t> mapq, absent, bases, qual;
+  std::vector<uint32_t> cigar;
+  std::vector<int64_t> cigar_off, base_off;
+  fcsbq_batch view() const {
+    fcsbq_batch b;
+    b.n = (int64_t)flag.size();
+    b.flag = flag.data(), b.ref_id = ref_id.data(), b.pos = pos.data(), b.mapq = mapq.data(), b.rg = rg.data();
+    b.cigar = cigar.data(), b.cigar_off = cigar_off.data(), b.n_cigar = (int64_t)cigar.size();
+    b.bases = bases.data(), b.qual = qual.data(), b.base_off = base_off.data(), b.n_bases = (int64_t)bases.size();
+    b.qual_absent = absent.data();
+    return b;
+  }
+};
+
+void flatten(const std::vector<BamRecord>& recs, const std::vector<int32_t>& rg, const std::vector<uint32_t>& order,
+             FlatBatch& f) {
+  const size_t n = order.size();
+  f.flag.resize(n), f.ref_id.resize(n), f.pos.resize(n), f.rg.resize(n), f.mapq.resize(n), f.absent.resize(n);
+  f.cigar_off.assign(n + 1, 0), f.base_off.assign(n + 1, 0);
+  for (size_t k = 0; k < n; ++k) {
+    const BamRecord& r = recs[order[k]];
+    f.flag[k] = r.flag, f.ref_id[k] = r.ref_id, f.pos[k] = r.pos, f.rg[k] = rg[order[k]], f.mapq[k] = r.mapq;
+    f.absent[k] = r.qual.size() != r.seq.size() || r.seq.empty();
+    f.cigar_off[k + 1] = f.cigar_off[k] + (int64_t)r.cigar.size();
+    f.base_off[k + 1] = f.base_off[k] + (int64_t)r.seq.size();
+  }
+  f.cigar.resize((size_t)f.cigar_off[n]);
+  f.bases.resize((size_t)f.base_off[n]);
+  f.qual.resize((size_t)f.base_off[n]);
+  parallel_for(n, host_threads(), [&](size_t k) {
+    const BamRecord& r = recs[order[k]];
+    if (!r.cigar.empty()) std::memcpy(f.cigar.data() + f.cigar_off[k], r.cigar.data(), 4 * r.cigar.size());
+    if (!r.seq.empty()) {
+      std::memcpy(f.bases.data() + f.base_off[k], r.seq.data(), r.seq.size());
+      if (f.absent[k]) std::memset(f.qual.data() + f.base_off[k], 0xff, r.seq.size());
+      else std::memcpy(f.qual.data() + f.base_off[k], r.qual.data(), r.seq.size());
+    }
+  });
+}
+
+// The job's input, read chunk by chunk: the records -L keeps, with their read group indices.
+class ChunkReader {
+ public:
+  ChunkReader(const BqsrJob& job) : bams_(input_bams(job.input)) {
+    reader_.reset(new BamReader(bams_[0]));
+    header_ = reader_->header();
+    read_groups(header_, ids_, names_);
+    for (size_t k = 0; k < ids_.size(); ++k) rg_index_.emplace(ids_[k], (int32_t)k);
+    regions_ = load_regions(job.intervals, header_);
+    chunk_ = (size_t)std::max(conf().get_int("bqsr.chunk_records"), 1);
+  }
+  const BamHeader& header() const { return header_; }
+  const std::vector<std::string>& rg_names() const { return names_; }
+  bool next(std::vector<BamRecord>& recs, std::vector<int32_t>& rg) {
+    recs.clear(), rg.clear();
+    BamRecord r;
+    std::string id;
+    while (recs.size() < chunk_) {
+      if (!reader_->next(r)) {
+        if (++file_ >= bams_.size()) break;
+        reader_.reset(new BamReader(bams_[file_]));
+        continue;
+      }
+      if (!regions_.keep(r)) continue;
+      int32_t g = -1;
+      if (r.get_aux_string("RG", id)) {
+        const auto it = rg_index_.find(id);
+        if (it != rg_index_.end()) g = it->second;
+      }
+      rg.push_back(g);
+      recs.push_back(std::move(r));
+    }
+    return !recs.empty();
+  }
+
+ private:
+  std::vector<std::string> bams_;
+  std::unique_ptr<BamReader> reader_;
+  size_t file_ = 0, chunk_ = 1;
+  BamHeader header_;
+  std::vector<std::string> ids_, names_;
+  std::unordered_map<std::string, int32_t> rg_index_;
+  Regions regions_;
+};
+
+// A device copy of the genome for the job's lifetime.
+struct DeviceRef {
+  fcsbq_ref* h = nullptr;
+  DeviceRef(int device, const BqGenome& g) {
+    if (device < 0) return;
+    if (bq_api().ref_create(device, g.bases.data(), g.ref_off.data(), (int32_t)g.ref_off.size() - 1, g.known.data(), &h) != FCS_OK)
+      throw failedCommand(std::string("[E::fcs-genome bqsr] fcsbq_ref_create: ") + bq_api().last_error());
+  }
+  ~DeviceRef() {
+    if (h) bq_api().ref_destroy(h);
+  }
+  DeviceRef(const DeviceRef&) = delete;
+  DeviceRef& operator=(const DeviceRef&) = delete;
+};
+
+struct CountTables {
+  int32_t n_rg = 0;
+  std::vector<int64_t> ctx, cyc;
+  explicit CountTables(int32_t n) : n_rg(n), ctx(2 * kBqCtxCells * (size_t)n, 0), cyc(2 * kBqCycCells * (size_t)n, 0) {}
+};
+
+void sum_tables(const CountTables& t, BqsrStats& st) {
+  for (size_t i = 0; i < t.cyc.size(); i += 2) st.observations += t.cyc[i], st.errors += t.cyc[i + 1];
+}
+
+// Pass 1: every chunk grouped by read group (stable) and counted into t.
+void count_pass(const BqsrJob& job, int device, CountTables& t, std::vector<std::string>& rg_names, BqsrStats& st) {
+  ChunkReader in(job);
+  rg_names = in.rg_names();
+  t = CountTables((int32_t)rg_names.size());
+  BqGenome g = load_genome(job.ref, in.header());
+  for (const std::string& k : job.known) load_known_sites(k, in.header(), g, st);
+  DeviceRef dref(device, g);
+  std::vector<BamRecord> recs;
+  std::vector<int32_t> rg;
+  std::vector<uint32_t> order;
+  FlatBatch f;
+  while (in.next(recs, rg)) {
+    order.resize(recs.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = (uint32_t)i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rg[a] < rg[b]; });
+    flatten(recs, rg, order, f);
+    const fcsbq_batch b = f.view();
+    for (int64_t r = 0; r < b.n; ++r)
+      st.counted += b.rg[r] >= 0 && !b.qual_absent[r] && !(b.flag[r] & 0x704) && b.mapq[r] != 0 && b.mapq[r] != 255;
+    st.records += b.n;
+    if (device >= 0) {
+      if (bq_api().count(dref.h, &b, t.n_rg, t.ctx.data(), t.cyc.data()) != FCS_OK)
+        throw failedCommand(std::string("[E::fcs-genome bqsr] fcsbq_count: ") + bq_api().last_error());
+    } else {
+      bqsr_count_host(g.view(), b, t.n_rg, t.ctx.data(), t.cyc.data(), host_threads());
+    }
+  }
+  sum_tables(t, st);
+}
+
+// Pass 2: every chunk's qualities rewritten from the tables, the records written in input order.
+void apply_pass(const BqsrJob& job, int device, const BqTables& tables, BqsrStats& st) {
+  ChunkReader in(job);
+  BamWriter w(job.output, in.header());
+  if (in.header().text.find("SO:coordinate") != std::string::npos) w.index_on_close();
+  std::vector<BamRecord> recs;
+  std::vector<int32_t> rg;
+  std::vector<uint32_t> order;
+  std::vector<uint8_t> out;
+  std::vector<const BamRecord*> ptrs;
+  FlatBatch f;
+  st.records = 0;
+  while (in.next(recs, rg)) {
+    order.resize(recs.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = (uint32_t)i;
+    flatten(recs, rg, order, f);
+    const fcsbq_batch b = f.view();
+    out.assign((size_t)b.n_bases + 1, 0);
+    if (device >= 0) {
+      if (bq_api().apply(device, &b, tables.n_rg, tables.base.data(), tables.dctx.data(), tables.dcyc.data(), out.data()) != FCS_OK)
+        throw failedCommand(std::string("[E::fcs-genome bqsr] fcsbq_apply: ") + bq_api().last_error());
+    } else {
+      bqsr_apply_host(b, tables, out.data(), host_threads());
+    }
+    parallel_for(recs.size(), host_threads(), [&](size_t k) {
+      if (b.rg[k] >= 0 && !b.qual_absent[k]) std::memcpy(recs[k].qual.data(), out.data() + b.base_off[k], recs[k].qual.size());
+    });
+    for (int64_t r = 0; r < b.n; ++r) st.recalibrated += b.rg[r] >= 0 && !b.qual_absent[r];
+    st.records += b.n;
+    ptrs.resize(recs.size());
+    for (size_t i = 0; i < recs.size(); ++i) ptrs[i] = &recs[i];
+    w.write_all(ptrs);
+  }
+  w.close();
+}
+
+std::vector<std::string> header_rg_names(const BqsrJob& job) {
+  BamReader in(input_bams(job.input)[0]);
+  std::vector<std::string> ids, names;
+  read_groups(in.header(), ids, names);
+  return names;
+}
+
+}  // namespace
+
+bool gpu_bqsr_available() {
+  const BqApi& a = bq_api();
+  return a.ref_create && a.ref_destroy && a.count && a.apply && a.last_error;
+}
+
+BqsrStats baserecal_run(const BqsrJob& job) {
+  const uint64_t t0 = now_us();
+  BqsrStats st;
+  const int device = device_of(job);
+  CountTables t(0);
+  std::vector<std::string> names;
+  count_pass(job, device, t, names, st);
+  write_file(job.report, bqsr_report_text(t.n_rg, t.ctx.data(), t.cyc.data(), names));
+  st.on_device = device >= 0;
+  st.seconds = (now_us() - t0) / 1e6;
+  return st;
+}
+
+BqsrStats printreads_run(const BqsrJob& job) {
+  const uint64_t t0 = now_us();
+  BqsrStats st;
+  const int device = device_of(job);
+  const std::vector<std::string> names = header_rg_names(job);
+  std::vector<int64_t> ctx, cyc;
+  bqsr_report_parse(read_file(job.report), names, ctx, cyc);
+  const BqTables tables = bqsr_finalize((int32_t)names.size(), ctx.data(), cyc.data());
+  apply_pass(job, device, tables, st);
+  st.on_device = device >= 0;
+  st.seconds = (now_us() - t0) / 1e6;
+  return st;
+}
+
+BqsrStats bqsr_run(const BqsrJob& job) {
+  const uint64_t t0 = now_us();
+  BqsrStats st;
+  const int device = device_of(job);
+  CountTables t(0);
+  std::vector<std::string> names;
+  count_pass(job, device, t, names, st);
+  if (!job.report.empty()) write_file(job.report, bqsr_report_text(t.n_rg, t.ctx.data(), t.cyc.data(), names));
+  const BqTables tables = bqsr_finalize(t.n_rg, t.ctx.data(), t.cyc.data());
+  apply_pass(job, device, tables, st);
+  st.on_device = device >= 0;
+  st.seconds = (now_us() - t0) / 1e6;
+  return st;
+}
+
+}  // namespace fcsg

@@ -11,6 +11,7 @@
 #include "bam_input.h"
 #include "caller.h"
 #include "bgzf.h"
+#include "bqsr.h"
 #include "common.h"
 #include "config.h"
 #include "executor.h"
@@ -497,6 +498,67 @@ int fcsg_markdup(int64_t n, const uint16_t* flag, const int32_t* ref_id, const i
     b.n_ref = n_ref, b.n_lib = n_lib;
     const MarkdupStats st = mark_duplicates_host(b, dup);
     stats[0] = st.examined, stats[1] = st.pairs, stats[2] = st.fragments, stats[3] = st.duplicates;
+  });
+}
+
+// The host statement of base quality recalibration (bqsr.h) over a flat batch
+// (include/fcsbq.h) and a flat reference: counts added to ctx / cyc, the
+// finalised tables, the applied qualities, and the report written and read
+// (names: the read groups' labels, one per line).
+int fcsg_bqsr_count(const fcsbq_batch* b, const uint8_t* ref_bases, const int64_t* ref_off, int32_t n_ref,
+                    const uint64_t* known, int32_t n_rg, int threads, int64_t* ctx, int64_t* cyc) {
+  return guard([&] {
+    BqRefView ref;
+    ref.bases = ref_bases, ref.ref_off = ref_off, ref.n_ref = n_ref, ref.known = known;
+    bqsr_count_host(ref, *b, n_rg, ctx, cyc, threads);
+  });
+}
+
+int fcsg_bqsr_finalize(int32_t n_rg, const int64_t* ctx, const int64_t* cyc, double* base, double* dctx, double* dcyc) {
+  return guard([&] {
+    const BqTables t = bqsr_finalize(n_rg, ctx, cyc);
+    std::memcpy(base, t.base.data(), 8 * t.base.size());
+    std::memcpy(dctx, t.dctx.data(), 8 * t.dctx.size());
+    std::memcpy(dcyc, t.dcyc.data(), 8 * t.dcyc.size());
+  });
+}
+
+int fcsg_bqsr_apply(const fcsbq_batch* b, int32_t n_rg, const double* base, const double* dctx, const double* dcyc,
+                    int threads, uint8_t* out_qual) {
+  return guard([&] {
+    BqTables t;
+    t.n_rg = n_rg;
+    t.base.assign(base, base + (size_t)n_rg * FCSBQ_NQ);
+    t.dctx.assign(dctx, dctx + (size_t)n_rg * kBqCtxCells);
+    t.dcyc.assign(dcyc, dcyc + (size_t)n_rg * kBqCycCells);
+    bqsr_apply_host(*b, t, out_qual, threads);
+  });
+}
+
+namespace {
+std::vector<std::string> split_lines(const char* s) {
+  std::vector<std::string> out;
+  std::string cur;
+  for (; *s; ++s)
+    if (*s == '\n') out.push_back(cur), cur.clear();
+    else cur += *s;
+  if (!cur.empty()) out.push_back(cur);
+  return out;
+}
+}  // namespace
+
+int fcsg_bqsr_report(int32_t n_rg, const int64_t* ctx, const int64_t* cyc, const char* names, char* buf, int cap) {
+  int rc = 0;
+  const int g = guard([&] { rc = copy_out(bqsr_report_text(n_rg, ctx, cyc, split_lines(names)), buf, cap); });
+  return g ? g : rc;
+}
+
+int fcsg_bqsr_report_parse(const char* text, const char* names, int64_t* ctx, int64_t* cyc) {
+  return guard([&] {
+    std::vector<int64_t> c, y;
+    bqsr_report_parse(text, split_lines(names), c, y);
+    std::memcpy(ctx, c.data(), 8 * c.size());
+    std::memcpy(cyc, y.data(), 8 * y.size());
   });
 }
 

@@ -64,6 +64,9 @@ void Config::init(const std::string& root_dir) {
           "align marks duplicates in each read group before the coordinate sort (unless --align-only)");
   declare("markdup.gpu", "false",
           "mark duplicates on the GPU (fcsdup_mark) instead of on the host (markdup, and align with markdup.in_align)");
+  declare("bqsr.gpu", "false",
+          "count covariates and rewrite qualities on the GPU (fcsbq_count / fcsbq_apply) instead of on the host (baserecal, printreads, bqsr)");
+  declare("bqsr.chunk_records", "1000000", "BAM records per chunk of baserecal / printreads / bqsr (one device call each)");
   // caller knobs (GATK HaplotypeCaller / Mutect2 argument defaults)
   declare("htc.min_base_quality", "10", "min base quality counted as evidence of activity");
   declare("htc.base_quality_threshold", "18", "PairHMM: base quals below this become 6");

@@ -27,6 +27,7 @@
 #include "executor.h"
 #include "fcship.h"
 #include "aligner.h"
+#include "bqsr_run.h"
 #include "intervals.h"
 #include "markdup.h"
 #include "sample_sheet.h"
@@ -440,6 +441,67 @@ int markdup_main(int argc, char** argv) {
   return 0;
 }
 
+// `fcs-genome baserecal | printreads | bqsr` (reference src/worker-bqsr.cpp:145-330,
+// which runs GATK's BaseRecalibrator and PrintReads / ApplyBQSR per contig
+// part): the BAM streams through host/bqsr_run.h in chunks, counted and
+// rewritten on the GPU (bqsr.gpu=true, include/fcsbq.h) or on the host.  With
+// bqsr.gpu=false the commands need no GPU.
+enum class BqsrCommand { kBaserecal, kPrintreads, kBqsr };
+
+int bqsr_main(int argc, char** argv, BqsrCommand cmd) {
+  const bool counts = cmd != BqsrCommand::kPrintreads, applies = cmd != BqsrCommand::kBaserecal;
+  const char* name = cmd == BqsrCommand::kBaserecal ? "baserecal" : cmd == BqsrCommand::kPrintreads ? "printreads" : "bqsr";
+  Args a;
+  common_opts(a);
+  a.add("ref", "r", false, true, "reference genome path");
+  a.add("input", "i", false, true, "input BAM file or dir");
+  if (cmd == BqsrCommand::kBaserecal) a.add("output", "o", false, true, "output BQSR file");
+  else a.add("output", "o", false, true, "output BAM file (a .bai is written when the input is coordinate-sorted)");
+  if (counts) a.add("knownSites", "K", false, false, "known sites for base recalibration (VCF or VCF.gz; may repeat)");
+  if (cmd == BqsrCommand::kPrintreads) a.add("bqsr", "b", false, true, "input BQSR file");
+  if (cmd == BqsrCommand::kBqsr) a.add("bqsr", "b", false, false, "output BQSR file (default: none is written)");
+  if (applies) a.add("merge-bam", "m", true, false, "accepted; the output is always one BAM");
+  a.add("gatk4", "g", true, false, "accepted; the rules are GATK 4's");
+  a.add("sample-id", cmd == BqsrCommand::kBaserecal ? "" : "t", false, false, "sample tag for log files");
+  a.add("intervalList", "L", false, false, "interval list file: only the records overlapping it are read");
+  try {
+    a.parse(argc, argv);
+  } catch (helpRequest&) {
+    std::cerr << "'fcs-genome " << name << "' options:\n" << a.help();
+    throw;
+  }
+  BqsrJob job;
+  job.ref = a.get("ref"), job.input = a.get("input");
+  if (a.has("intervalList")) job.intervals = a.get("intervalList");
+  if (!is_regular_file(job.ref)) throw fileNotFound(job.ref);
+  if (!path_exists(job.input)) throw fileNotFound(job.input);
+  if (!job.intervals.empty() && !is_regular_file(job.intervals)) throw fileNotFound(job.intervals);
+  if (counts) {
+    job.known = a.all("knownSites");
+    for (const std::string& k : job.known)
+      if (!is_regular_file(k)) throw fileNotFound(k);
+  }
+  const std::string output = a.get("output");
+  if (cmd == BqsrCommand::kBaserecal) job.report = output;
+  else job.output = output, job.report = a.get("bqsr");
+  if (cmd == BqsrCommand::kPrintreads && !is_regular_file(job.report)) throw fileNotFound(job.report);
+  if (!a.has("force")) {
+    if (path_exists(output)) throw invalidParam("output " + output + " exists (use -f)");
+    if (cmd == BqsrCommand::kBqsr && !job.report.empty() && path_exists(job.report))
+      throw invalidParam("output " + job.report + " exists (use -f)");
+  }
+  if (conf().get_bool("bqsr.gpu")) job.device = slots().front();
+  const BqsrStats st = cmd == BqsrCommand::kBaserecal ? baserecal_run(job)
+                       : cmd == BqsrCommand::kPrintreads ? printreads_run(job) : bqsr_run(job);
+  std::cerr << "[fcs-genome " << name << "] " << st.records << " records";
+  if (counts)
+    std::cerr << ", " << st.counted << " counted, " << st.observations << " observations, " << st.errors << " errors, "
+              << st.known_sites << " known sites (" << st.known_skipped << " on unknown contigs)";
+  if (applies) std::cerr << ", " << st.recalibrated << " recalibrated";
+  std::cerr << ", " << st.seconds << " s (" << (st.on_device ? "GPU" : "host") << ")" << std::endl;
+  return 0;
+}
+
 // `fcs-genome index -r ref.fasta`: the aligner's FMD-index, saved next to the
 // FASTA (<ref>.fcsidx) so that align maps it instead of building one per run
 // (bwa-flow reads the prebuilt bwa index; the reference expects it beside the
@@ -568,6 +630,9 @@ int print_help() {
                "Usage: fcs-genome [command] <options>\n\nCommands:\n"
                "  align           align FASTQ reads into a sorted BAM (GPU banded SW)\n"
                "  markdup         mark duplicate reads of a BAM (GPU sort + segmented arg-max)\n"
+               "  baserecal       base recalibration table of a BAM against known sites (GPU covariate counting)\n"
+               "  printreads      apply a base recalibration table to a BAM (GPU table lookup)\n"
+               "  bqsr            baserecal and printreads in one run\n"
                "  htc             variant calling, HaplotypeCaller-style (GPU PairHMM)\n"
                "  mutect2         somatic variant calling, tumor/normal (GPU PairHMM)\n"
                "  conf            print configuration keys\n"
@@ -608,6 +673,9 @@ int main(int argc, char** argv) {
     else if (cmd == "mutect2") ret = mutect2_main(argc - 1, argv + 1);
     else if (cmd == "align" || cmd == "al") ret = align_main(argc - 1, argv + 1);
     else if (cmd == "markdup" || cmd == "md") ret = markdup_main(argc - 1, argv + 1);
+    else if (cmd == "baserecal") ret = bqsr_main(argc - 1, argv + 1, BqsrCommand::kBaserecal);
+    else if (cmd == "printreads" || cmd == "pr") ret = bqsr_main(argc - 1, argv + 1, BqsrCommand::kPrintreads);
+    else if (cmd == "bqsr") ret = bqsr_main(argc - 1, argv + 1, BqsrCommand::kBqsr);
     else if (cmd == "synth") ret = synth_main(argc - 1, argv + 1);
     else if (cmd == "index") ret = index_main(argc - 1, argv + 1);
     else if (cmd == "conf") {
