@@ -1,0 +1,96 @@
+// Depth of coverage (DESIGN §2 [EXT], §4.11): what one base of one record adds.
+// One text for the gfx950 kernels (depth.hip) and the host check
+// (tools/micro/depth_test.cpp); everything works over caller spans, one base
+// at a time, so that a lane can take a base.
+//
+//   dp_counted    the record filter (ref_id, CIGAR, flags, MAPQ bounds)
+//   dp_span       the read bases the CIGAR covers and the reference span
+//   dp_site       whether read base i is aligned (M / = / X), and where
+//   dp_base_ok    the base quality bounds
+//   dp_in_window  the window offset of a counted position, or -1
+//   dp_run_first / dp_run_last   the ends of the maximal runs of counted bases
+//                 at consecutive positions among 64 neighbours
+//   dp_bin / dp_quantile         the histogram bin and the granular quantile
+#pragma once
+
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define DP_HD __host__ __device__ __forceinline__
+#else
+#define DP_HD inline
+#endif
+
+namespace fcs {
+
+constexpr int kDpBins = 501, kDpAbove = 15, kDpPieceMax = 65536;
+constexpr uint16_t kDpFlagFilter = 0x4 | 0x100 | 0x200 | 0x400;
+constexpr int kDpStatusField = 1, kDpStatusRef = 2, kDpStatusOverflow = 4;
+
+DP_HD bool dp_counted(uint16_t flag, int32_t ref_id, int64_t n_ops, uint8_t mapq, int32_t min_mapq, int32_t max_mapq) {
+  return ref_id >= 0 && n_ops > 0 && (flag & kDpFlagFilter) == 0 && (int32_t)mapq >= min_mapq && (int32_t)mapq <= max_mapq;
+}
+
+// One pass over the record's n_ops CIGAR words (len << 4 | op): the read bases
+// of S / M / I / = / X and the reference bases of M / D / N / = / X.
+DP_HD void dp_span(const uint32_t* cigar, int64_t n_ops, int64_t& covered, int64_t& ref_len) {
+  covered = ref_len = 0;
+  for (int64_t k = 0; k < n_ops; ++k) {
+    const uint32_t op = cigar[k] & 15u;
+    const int64_t len = (int64_t)(cigar[k] >> 4);
+    if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) covered += len;
+    if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) ref_len += len;
+  }
+}
+
+// Read base i (0 <= i < covered): true, with its reference position in p, when it lies in M, = or X.
+DP_HD bool dp_site(const uint32_t* cigar, int64_t n_ops, int32_t pos, int64_t i, int64_t& p) {
+  int64_t q = 0, r = pos;
+  for (int64_t k = 0; k < n_ops; ++k) {
+    const uint32_t op = cigar[k] & 15u;
+    const int64_t len = (int64_t)(cigar[k] >> 4);
+    if (op == 0u || op == 7u || op == 8u) {
+      if (i < q + len) {
+        p = r + (i - q);
+        return true;
+      }
+      q += len, r += len;
+    } else if (op == 1u || op == 4u) {
+      if (i < q + len) break;
+      q += len;
+    } else if (op == 2u || op == 3u) {
+      r += len;
+    }
+  }
+  p = 0;
+  return false;
+}
+
+DP_HD bool dp_base_ok(int q, int32_t min_baseq, int32_t max_baseq) { return q >= min_baseq && q <= max_baseq; }
+
+// The window offset of position p of a contig of clen bases, or -1 outside the
+// window [w0, w0 + wlen) or the contig.
+DP_HD int32_t dp_in_window(int64_t p, int64_t w0, int64_t wlen, int64_t clen) {
+  return p >= 0 && p < clen && p >= w0 && p < w0 + wlen ? (int32_t)(p - w0) : -1;
+}
+
+// Lane `lane` of 64 holds window offset off (>= 0: counted).  counted is the
+// ballot of off >= 0, prev / next the neighbours' offsets (lane - 1, lane + 1).
+DP_HD bool dp_run_first(int lane, unsigned long long counted, int32_t off, int32_t prev) {
+  return off >= 0 && (lane == 0 || !((counted >> (lane - 1)) & 1u) || prev != off - 1);
+}
+DP_HD bool dp_run_last(int lane, unsigned long long counted, int32_t off, int32_t next) {
+  return off >= 0 && (lane == 63 || !((counted >> (lane + 1)) & 1u) || next != off + 1);
+}
+
+DP_HD int dp_bin(uint32_t depth) { return depth < (uint32_t)(kDpBins - 1) ? (int)depth : kDpBins - 1; }
+
+// Bin b is the k-th granular quantile (k = 1, 2, 3) of n > 0 loci when the
+// counts up to and including it reach k/4 of n and those before it do not.
+DP_HD bool dp_is_quantile(uint64_t cum_before, uint64_t cum_with, uint64_t n, int k) {
+  return 4 * cum_with >= (uint64_t)k * n && 4 * cum_before < (uint64_t)k * n;
+}
+DP_HD uint32_t dp_reported(int bin) { return bin < 1 ? 1u : (uint32_t)bin; }
+
+}  // namespace fcs

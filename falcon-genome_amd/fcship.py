@@ -874,3 +874,97 @@ def bq_apply(arrays, base, dctx, dcyc, device: int = 0, out=None, **kw):
     check(lib.fcsbq_apply(device, C.addressof(b), base.shape[0], base.ctypes.data, dctx.ctypes.data, dcyc.ctypes.data,
                           out.ctypes.data))
     return out[:len(arrays[7])]
+
+
+# ---------------------------------------------------------------- depth of coverage (include/fcsdp.h)
+DP_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "fcsdp.h")
+FCSDP_BINS, FCSDP_PIECE_MAX, FCSDP_WINDOW_MAX, FCSDP_ABOVE = 501, 65536, 1 << 30, 15
+FCSDP_STATUS_FIELD, FCSDP_STATUS_REF, FCSDP_STATUS_OVERFLOW = 1, 2, 4
+
+
+class DpBatch(C.Structure):
+    _fields_ = [("n", C.c_int64), ("flag", C.c_void_p), ("ref_id", C.c_void_p), ("pos", C.c_void_p),
+                ("mapq", C.c_void_p), ("cigar", C.c_void_p), ("cigar_off", C.c_void_p), ("n_cigar", C.c_int64),
+                ("bases", C.c_void_p), ("qual", C.c_void_p), ("base_off", C.c_void_p), ("n_bases", C.c_int64),
+                ("qual_absent", C.c_void_p)]
+
+
+class DpParams(C.Structure):
+    _fields_ = [("min_mapq", C.c_int32), ("max_mapq", C.c_int32), ("min_baseq", C.c_int32), ("max_baseq", C.c_int32),
+                ("include_deletions", C.c_int32)]
+
+
+class DpWindow(C.Structure):
+    _fields_ = [("ref_id", C.c_int32), ("reserved", C.c_int32), ("start", C.c_int64), ("len", C.c_int64),
+                ("contig_len", C.c_int64)]
+
+
+DP_PIECE = np.dtype([("start", np.int32), ("end", np.int32), ("long_index", np.int32), ("reserved", np.int32)])
+DP_SUMMARY = np.dtype([("total", np.uint64), ("loci", np.uint32), ("above", np.uint32), ("q1", np.uint32),
+                       ("median", np.uint32), ("q3", np.uint32), ("reserved", np.uint32)])
+
+_sig("fcsdp_count", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+_sig("fcsdp_stats", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                              C.c_void_p, C.c_void_p])
+_sig("fcsdp_workspace_bytes", C.c_int64, [C.c_int64])
+_sig("fcsdp_runs_dev", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+_sig("fcsdp_scan_dev", C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])
+_sig("fcsdp_stats_dev", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+
+
+def dp_header_symbols() -> list[str]:
+    """Function names declared in include/fcsdp.h."""
+    import re
+    txt = re.sub(r"/\*.*?\*/", "", open(DP_HEADER_PATH).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(fcsdp_[a-z0-9_]+)\s*\(", txt)))
+
+
+_DP_DTYPES = (np.uint16, np.int32, np.int32, np.uint8, np.uint32, np.int64, np.uint8, np.int64, np.uint8)
+
+
+def dp_arrays(flag, ref_id, pos, mapq, cigar, cigar_off, qual, base_off, qual_absent):
+    """The batch's arrays in the dtypes fcsdp_batch names."""
+    return tuple(np.ascontiguousarray(a, t) for a, t in zip(
+        (flag, ref_id, pos, mapq, cigar, cigar_off, qual, base_off, qual_absent), _DP_DTYPES))
+
+
+def dp_batch(arrays, n=None, n_cigar=None, n_bases=None) -> DpBatch:
+    """fcsdp_batch over host arrays (dp_arrays' tuple, which the caller keeps alive)."""
+    flag, ref_id, pos, mapq, cigar, cigar_off, qual, base_off, absent = arrays
+    return DpBatch(len(flag) if n is None else n, _ptr(flag), _ptr(ref_id), _ptr(pos), _ptr(mapq), _ptr(cigar),
+                   _ptr(cigar_off), len(cigar) if n_cigar is None else n_cigar, 0, _ptr(qual), _ptr(base_off),
+                   len(qual) if n_bases is None else n_bases, _ptr(absent))
+
+
+def dp_params(min_mapq=-1, max_mapq=2147483647, min_baseq=-1, max_baseq=127, include_deletions=False) -> DpParams:
+    return DpParams(min_mapq, max_mapq, min_baseq, max_baseq, 1 if include_deletions else 0)
+
+
+def dp_count(arrays, window, params=None, depth=None, device: int = 0, **kw):
+    """fcsdp_count: the batch's depths over window = (ref_id, start, len, contig_len), added to depth (new when None)."""
+    arrays = dp_arrays(*arrays)
+    b = dp_batch(arrays, **kw)
+    ref_id, start, length, contig_len = window
+    w = DpWindow(ref_id, 0, start, length, contig_len)
+    prm = params if params is not None else dp_params()
+    depth = np.zeros(length, np.uint32) if depth is None else depth
+    assert depth.dtype == np.uint32 and depth.flags.c_contiguous and len(depth) == length
+    check(lib.fcsdp_count(device, C.addressof(b), C.addressof(prm), C.addressof(w), _ptr(depth)))
+    return depth
+
+
+def dp_stats(depth, bitmap, pieces, n_long=0, hist=None, long_hist=None, device: int = 0):
+    """fcsdp_stats: (hist[501], long_hist[n_long, 501], summary[n_pieces] of DP_SUMMARY); pieces: (start, end, long_index)."""
+    depth = np.ascontiguousarray(depth, np.uint32)
+    bitmap = np.ascontiguousarray(bitmap, np.uint64)
+    assert len(bitmap) >= (len(depth) + 63) // 64
+    pc = np.zeros(len(pieces), DP_PIECE)
+    for k, (s, e, li) in enumerate(pieces):
+        pc[k] = (s, e, li, 0)
+    hist = np.zeros(FCSDP_BINS, np.uint64) if hist is None else hist
+    long_hist = np.zeros((n_long, FCSDP_BINS), np.uint64) if long_hist is None else long_hist
+    summary = np.zeros(len(pieces), DP_SUMMARY)
+    check(lib.fcsdp_stats(device, _ptr(depth), _ptr(bitmap), len(depth), _ptr(pc), len(pc), n_long, hist.ctypes.data,
+                          _ptr(long_hist), _ptr(summary)))
+    return hist, long_hist, summary

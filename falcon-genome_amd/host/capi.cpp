@@ -12,6 +12,7 @@
 #include "caller.h"
 #include "bgzf.h"
 #include "bqsr.h"
+#include "depth.h"
 #include "common.h"
 #include "config.h"
 #include "executor.h"
@@ -560,6 +561,18 @@ int fcsg_bqsr_report_parse(const char* text, const char* names, int64_t* ctx, in
     std::memcpy(ctx, c.data(), 8 * c.size());
     std::memcpy(cyc, y.data(), 8 * y.size());
   });
+}
+
+// The host statement of depth of coverage (depth.h) over a flat batch and a
+// window (include/fcsdp.h): depths added to depth[len], and the statistics of
+// a window's pieces.
+int fcsg_depth_count(const fcsdp_batch* b, const fcsdp_params* prm, const fcsdp_window* w, int threads, uint32_t* depth) {
+  return guard([&] { depth_count_host(*b, *prm, *w, depth, threads); });
+}
+
+int fcsg_depth_stats(const uint32_t* depth, const uint64_t* bitmap, int64_t len, const fcsdp_piece* pieces, int64_t n_pieces,
+                     int32_t n_long, int threads, uint64_t* hist, uint64_t* long_hist, fcsdp_summary* summary) {
+  return guard([&] { depth_stats_host(depth, bitmap, len, pieces, n_pieces, n_long, hist, long_hist, summary, threads); });
 }
 
 int fcsg_bam_index(const char* bam) {

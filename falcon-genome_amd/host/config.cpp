@@ -67,6 +67,16 @@ void Config::init(const std::string& root_dir) {
   declare("bqsr.gpu", "false",
           "count covariates and rewrite qualities on the GPU (fcsbq_count / fcsbq_apply) instead of on the host (baserecal, printreads, bqsr)");
   declare("bqsr.chunk_records", "1000000", "BAM records per chunk of baserecal / printreads / bqsr (one device call each)");
+  declare("depth.gpu", "false",
+          "count depths and summarise windows on the GPU (fcsdp_count / fcsdp_stats) instead of on the host (depth)");
+  declare("depth.chunk_records", "1000000", "BAM records per chunk of depth (one device call per chunk and window)");
+  declare("depth.window_bp", "67108864", "loci per window of depth at most (one depth array each; DESIGN 4.11)");
+  declare("depth.min_mapq", "-1", "depth: records with a lower MAPQ are not counted");
+  declare("depth.max_mapq", "2147483647", "depth: records with a higher MAPQ are not counted");
+  declare("depth.min_baseq", "-1", "depth: bases with a lower quality are not counted");
+  declare("depth.max_baseq", "127", "depth: bases with a higher quality are not counted");
+  declare("depth.include_deletions", "false", "depth: every deleted position adds 1");
+  declare("depth.include_ref_n", "false", "depth: loci whose reference base is N take part");
   // caller knobs (GATK HaplotypeCaller / Mutect2 argument defaults)
   declare("htc.min_base_quality", "10", "min base quality counted as evidence of activity");
   declare("htc.base_quality_threshold", "18", "PairHMM: base quals below this become 6");

@@ -1,0 +1,469 @@
+// The depth command (depth_run.h): the BAM streams in chunks of
+// depth.chunk_records; the genome is walked in windows of at most
+// depth.window_bp loci over the contigs that hold intervals; a chunk's records
+// are given to every window they overlap and clipped to it; a window is
+// summarised and written once the stream has passed its end.
+#include "depth_run.h"
+
+#include <dlfcn.h>
+
+#include <algorithm>
+#include <climits>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <set>
+#include <sstream>
+
+#include "bam.h"
+#include "common.h"
+#include "config.h"
+#include "depth.h"
+#include "fasta.h"
+#include "fcship.h"
+#include "intervals.h"
+
+namespace fcsg {
+
+namespace {
+
+struct DpApi {
+  decltype(&fcsdp_count) count = nullptr;
+  decltype(&fcsdp_stats) stats = nullptr;
+  const char* (*last_error)() = nullptr;
+};
+
+const DpApi& dp_api() {
+  static const DpApi A = [] {
+    DpApi a;
+    a.count = reinterpret_cast<decltype(a.count)>(dlsym(RTLD_DEFAULT, "fcsdp_count"));
+    a.stats = reinterpret_cast<decltype(a.stats)>(dlsym(RTLD_DEFAULT, "fcsdp_stats"));
+    a.last_error = reinterpret_cast<decltype(a.last_error)>(dlsym(RTLD_DEFAULT, "fcs_last_error"));
+    return a;
+  }();
+  return A;
+}
+
+// The device the job runs on, or -1 (with one log line when the library lacks the entry points).
+int device_of(const DepthJob& job) {
+  if (job.device < 0) return -1;
+  if (gpu_depth_available()) return job.device;
+  static std::once_flag said;
+  std::call_once(said, [] {
+    std::fprintf(stderr, "[fcs-genome depth] depth.gpu: the loaded libfcship has no fcsdp_count entry point; "
+                         "depths are counted on the host\n");
+  });
+  return -1;
+}
+
+int host_threads() { return (int)std::min<unsigned>(host_cpus(), 16); }
+
+std::vector<std::string> input_bams(const std::string& input) {
+  if (is_regular_file(input)) return {input};
+  if (!is_directory(input)) throw fileNotFound(input);
+  std::vector<std::string> names = list_dir(input, ".bam");
+  std::sort(names.begin(), names.end());
+  std::vector<std::string> out;
+  for (const std::string& n : names) out.push_back(n.find('/') == std::string::npos ? input + "/" + n : n);
+  if (out.empty()) throw fileNotFound(input + "/*.bam");
+  return out;
+}
+
+// The single distinct SM of the header's @RG lines.
+std::string sample_of(const BamHeader& h) {
+  std::set<std::string> sm;
+  std::istringstream ss(h.text);
+  for (std::string line; std::getline(ss, line);) {
+    if (line.rfind("@RG", 0) != 0) continue;
+    for (size_t p = 0; p < line.size();) {
+      const size_t e = std::min(line.find('\t', p), line.size());
+      if (line.compare(p, 3, "SM:") == 0 && e > p + 3) sm.insert(line.substr(p + 3, e - p - 3));
+      p = e + 1;
+    }
+  }
+  if (sm.empty()) throw invalidParam("the BAM header names no sample (no @RG line with SM)");
+  if (sm.size() > 1) {
+    std::string all;
+    for (const std::string& s : sm) all += (all.empty() ? "" : ", ") + s;
+    throw invalidParam("the BAM header names " + std::to_string(sm.size()) + " samples (" + all + "); depth takes one");
+  }
+  return *sm.begin();
+}
+
+struct Iv {
+  int32_t ref;
+  int64_t start, end;  // 0-based half-open
+};
+
+// -L sorted by header contig order with overlapping and abutting intervals merged, or one interval per contig.
+std::vector<Iv> load_intervals(const std::string& path, const BamHeader& h) {
+  std::vector<Iv> iv;
+  if (path.empty()) {
+    for (size_t c = 0; c < h.names.size(); ++c) iv.push_back({(int32_t)c, 0, h.lengths[c]});
+    return iv;
+  }
+  for (const Interval& i : read_regions(path)) {
+    const int c = h.ref_index(i.chrom);
+    if (c < 0) throw invalidParam("contig " + i.chrom + " of " + path + " is not in the BAM header");
+    const int64_t s = std::max<int64_t>(i.lb - 1, 0), e = std::min<int64_t>(i.ub, h.lengths[(size_t)c]);
+    if (s >= e) throw invalidParam("interval " + i.chrom + ":" + std::to_string(i.lb) + "-" + std::to_string(i.ub) + " of " + path +
+                                   " is empty or beyond its contig");
+    iv.push_back({(int32_t)c, s, e});
+  }
+  std::sort(iv.begin(), iv.end(), [](const Iv& a, const Iv& b) { return a.ref != b.ref ? a.ref < b.ref : a.start < b.start; });
+  std::vector<Iv> out;
+  for (const Iv& i : iv) {
+    if (!out.empty() && out.back().ref == i.ref && i.start <= out.back().end) out.back().end = std::max(out.back().end, i.end);
+    else out.push_back(i);
+  }
+  return out;
+}
+
+struct Part {
+  size_t interval;
+  int64_t start, end;  // window offsets
+};
+
+struct Window {
+  fcsdp_window w;
+  std::vector<Part> parts;
+};
+
+// One chunk of records as an fcsdp_batch over its own arrays.
+struct FlatBatch {
+  std::vector<uint16_t> flag;
+  std::vector<int32_t> ref_id, pos;
+  std::vector<uint8_t> mapq, absent, qual;
+  std::vector<uint32_t> cigar;
+  std::vector<int64_t> cigar_off, base_off, max_end;  // max_end: the running maximum of the records' ends on their contig
+  // Records [lo, hi) as a batch that keeps the chunk's offsets.
+  fcsdp_batch view(size_t lo, size_t hi) const {
+    fcsdp_batch b;
+    b.n = (int64_t)(hi - lo);
+    b.flag = flag.data() + lo, b.ref_id = ref_id.data() + lo, b.pos = pos.data() + lo, b.mapq = mapq.data() + lo;
+    b.cigar = cigar.data(), b.cigar_off = cigar_off.data() + lo, b.n_cigar = (int64_t)cigar.size();
+    b.bases = nullptr, b.qual = qual.data(), b.base_off = base_off.data() + lo, b.n_bases = (int64_t)qual.size();
+    b.qual_absent = absent.data() + lo;
+    return b;
+  }
+};
+
+void flatten(const std::vector<BamRecord>& recs, FlatBatch& f) {
+  const size_t n = recs.size();
+  f.flag.resize(n), f.ref_id.resize(n), f.pos.resize(n), f.mapq.resize(n), f.absent.resize(n), f.max_end.resize(n);
+  f.cigar_off.assign(n + 1, 0), f.base_off.assign(n + 1, 0);
+  for (size_t k = 0; k < n; ++k) {
+    const BamRecord& r = recs[k];
+    f.flag[k] = r.flag, f.ref_id[k] = r.ref_id, f.pos[k] = r.pos, f.mapq[k] = r.mapq;
+    f.absent[k] = r.qual.size() != r.seq.size() || r.seq.empty();
+    f.cigar_off[k + 1] = f.cigar_off[k] + (int64_t)r.cigar.size();
+    f.base_off[k + 1] = f.base_off[k] + (int64_t)r.seq.size();
+    const int64_t end = r.end();
+    f.max_end[k] = k > 0 && recs[k - 1].ref_id == r.ref_id ? std::max(f.max_end[k - 1], end) : end;
+  }
+  f.cigar.resize((size_t)f.cigar_off[n]);
+  f.qual.resize((size_t)f.base_off[n]);
+  parallel_for(n, host_threads(), [&](size_t k) {
+    const BamRecord& r = recs[k];
+    if (!r.cigar.empty()) std::memcpy(f.cigar.data() + f.cigar_off[k], r.cigar.data(), 4 * r.cigar.size());
+    if (!r.seq.empty()) {
+      if (f.absent[k]) std::memset(f.qual.data() + f.base_off[k], 0xff, r.seq.size());
+      else std::memcpy(f.qual.data() + f.base_off[k], r.qual.data(), r.seq.size());
+    }
+  });
+}
+
+// The sort key of a record: unmapped records without a contig come last.
+std::pair<int64_t, int64_t> key_of(int32_t ref_id, int32_t pos) { return {ref_id < 0 ? (int64_t)INT32_MAX + 1 : ref_id, pos}; }
+
+class Run {
+ public:
+  explicit Run(const DepthJob& job) : job_(job), device_(device_of(job)), bams_(input_bams(job.input)) {
+    reader_.reset(new BamReader(bams_[0]));
+    header_ = reader_->header();
+    st_.sample = sample_of(header_);
+    const Reference ref = load_fasta(job.ref);
+    contigs_.resize(header_.names.size());
+    for (size_t k = 0; k < header_.names.size(); ++k) {
+      const int c = ref.index(header_.names[k]);
+      if (c < 0) throw invalidParam("contig " + header_.names[k] + " of the BAM header is not in " + job.ref);
+      contigs_[k] = ref.contigs[(size_t)c].seq;
+      if ((int64_t)contigs_[k].size() != header_.lengths[k])
+        throw invalidParam("contig " + header_.names[k] + " has " + std::to_string(header_.lengths[k]) +
+                           " bases in the BAM header and " + std::to_string(contigs_[k].size()) + " in " + job.ref);
+    }
+    Config& cf = conf();
+    prm_.min_mapq = cf.get_int("depth.min_mapq"), prm_.max_mapq = cf.get_int("depth.max_mapq");
+    prm_.min_baseq = cf.get_int("depth.min_baseq"), prm_.max_baseq = cf.get_int("depth.max_baseq");
+    prm_.include_deletions = cf.get_bool("depth.include_deletions");
+    if (prm_.min_mapq > prm_.max_mapq || prm_.min_baseq > prm_.max_baseq)
+      throw invalidParam("depth.min_mapq / max_mapq or depth.min_baseq / max_baseq: a lower bound above its upper bound");
+    include_ref_n_ = cf.get_bool("depth.include_ref_n");
+    chunk_ = (size_t)std::max(cf.get_int("depth.chunk_records"), 1);
+    window_bp_ = std::clamp<int64_t>(cf.get_int("depth.window_bp"), 1, FCSDP_WINDOW_MAX);
+    intervals_ = load_intervals(job.intervals, header_);
+    cut_windows();
+    hist_.assign(FCSDP_BINS, 0);
+    long_hist_.assign((size_t)FCSDP_BINS * n_long_, 0);
+  }
+
+  DepthRunStats run() {
+    const uint64_t t0 = now_us();
+    if (!job_.omit_base) {
+      locus_.open(job_.output, std::ios::binary | std::ios::trunc);
+      if (!locus_) throw failedCommand("[E::fcs-genome depth] cannot write " + job_.output);
+      locus_ << depth_locus_header(st_.sample);
+    }
+    try {
+      stream();
+    } catch (...) {  // a refused run leaves no partial per-locus file
+      if (!job_.omit_base) locus_.close(), remove_path(job_.output);
+      throw;
+    }
+    st_.windows = (int64_t)windows_.size(), st_.intervals = (int64_t)intervals_.size();
+    st_.total = total_;
+    for (uint64_t v : hist_) st_.loci += v;
+    st_.on_device = device_ >= 0;
+    st_.seconds = (now_us() - t0) / 1e6;
+    return st_;
+  }
+
+ private:
+  // The chunks in order: each is counted into the windows it overlaps, and every window the stream has passed is finished.
+  void stream() {
+    std::vector<BamRecord> recs;
+    FlatBatch f;
+    while (next_chunk(recs)) {
+      st_.records += (int64_t)recs.size();
+      flatten(recs, f);
+      count_chunk(f);
+      const auto last = key_of(f.ref_id.back(), f.pos.back());
+      while (cur_ < windows_.size() && (windows_[cur_].w.ref_id < last.first ||
+                                        (windows_[cur_].w.ref_id == last.first &&
+                                         windows_[cur_].w.start + windows_[cur_].w.len <= last.second)))
+        finish_window(cur_++);
+      if (interrupted()) throw interruptedError();
+    }
+    while (cur_ < windows_.size()) finish_window(cur_++);
+    write_files();
+  }
+
+  // Windows of at most window_bp loci from each contig's first interval start to its last interval end;
+  // an interval cut by a window edge or longer than a piece gets a row of long_hist.
+  void cut_windows() {
+    rows_.resize(intervals_.size());
+    long_index_.assign(intervals_.size(), -1);
+    for (size_t a = 0; a < intervals_.size();) {
+      size_t b = a;
+      while (b < intervals_.size() && intervals_[b].ref == intervals_[a].ref) ++b;
+      const int32_t ref = intervals_[a].ref;
+      size_t k = a;
+      for (int64_t s = intervals_[a].start; s < intervals_[b - 1].end; s += window_bp_) {
+        Window win;
+        win.w.ref_id = ref, win.w.reserved = 0, win.w.start = s;
+        win.w.len = std::min(window_bp_, intervals_[b - 1].end - s), win.w.contig_len = header_.lengths[(size_t)ref];
+        const int64_t e = s + win.w.len;
+        while (k < b && intervals_[k].end <= s) ++k;
+        for (size_t j = k; j < b && intervals_[j].start < e; ++j)
+          win.parts.push_back({j, std::max(intervals_[j].start, s) - s, std::min(intervals_[j].end, e) - s});
+        if (!win.parts.empty()) windows_.push_back(std::move(win));
+      }
+      a = b;
+    }
+    std::vector<int> n_parts(intervals_.size(), 0);
+    for (const Window& w : windows_)
+      for (const Part& p : w.parts) ++n_parts[p.interval];
+    for (size_t j = 0; j < intervals_.size(); ++j) {
+      const Iv& i = intervals_[j];
+      if (n_parts[j] > 1 || i.end - i.start > FCSDP_PIECE_MAX) long_index_[j] = n_long_++;
+      rows_[j].name = header_.names[(size_t)i.ref] + ":" + std::to_string(i.start + 1) +
+                      (i.end - i.start > 1 ? "-" + std::to_string(i.end) : "");
+    }
+  }
+
+  bool next_chunk(std::vector<BamRecord>& recs) {
+    recs.clear();
+    BamRecord r;
+    while (recs.size() < chunk_) {
+      if (!reader_->next(r)) {
+        if (++file_ >= bams_.size()) break;
+        reader_.reset(new BamReader(bams_[file_]));
+        continue;
+      }
+      const auto key = key_of(r.ref_id, r.pos);
+      if (key < last_key_) {
+        auto where = [&](int64_t ref, int64_t pos) {
+          return (ref >= 0 && ref < (int64_t)header_.names.size() ? header_.names[(size_t)ref] : std::string("*")) + ":" +
+                 std::to_string(pos + 1);
+        };
+        throw invalidParam("the input is not coordinate-sorted: record " + r.name + " at " + where(r.ref_id, r.pos) +
+                           " follows one at " + where(last_key_.first, last_key_.second));
+      }
+      last_key_ = key;
+      recs.push_back(std::move(r));
+    }
+    return !recs.empty();
+  }
+
+  // The chunk's records given to every window they overlap.
+  void count_chunk(const FlatBatch& f) {
+    const size_t n = f.flag.size();
+    struct Seg {
+      int32_t ref;
+      size_t a, b;
+    };
+    std::vector<Seg> segs;  // the chunk's runs of records on one contig, in contig order
+    for (size_t k = 0; k < n && f.ref_id[k] >= 0; ++k) {
+      if (segs.empty() || segs.back().ref != f.ref_id[k]) segs.push_back({f.ref_id[k], k, k});
+      segs.back().b = k + 1;
+    }
+    if (segs.empty()) return;
+    size_t si = 0;
+    for (size_t wi = cur_; wi < windows_.size(); ++wi) {
+      const fcsdp_window& w = windows_[wi].w;
+      while (si < segs.size() && segs[si].ref < w.ref_id) ++si;
+      if (si == segs.size()) break;
+      if (segs[si].ref > w.ref_id) continue;
+      const size_t a = segs[si].a, b = segs[si].b;
+      if (si + 1 == segs.size() && f.max_end[b - 1] <= w.start) break;  // later windows hold nothing of this chunk
+      // the records that start before the window's end and whose running maximum end lies beyond its start
+      const size_t hi = (size_t)(std::lower_bound(f.pos.begin() + (long)a, f.pos.begin() + (long)b, w.start + w.len,
+                                                  [](int32_t p, int64_t e) { return (int64_t)p < e; }) - f.pos.begin());
+      const size_t lo = (size_t)(std::upper_bound(f.max_end.begin() + (long)a, f.max_end.begin() + (long)hi, w.start) -
+                                 f.max_end.begin());
+      if (lo >= hi) continue;
+      std::vector<uint32_t>& depth = open_[wi];
+      if (depth.empty()) depth.assign((size_t)w.len, 0);
+      const fcsdp_batch view = f.view(lo, hi);
+      if (device_ >= 0) {
+        if (dp_api().count(device_, &view, &prm_, &w, depth.data()) != FCS_OK)
+          throw failedCommand(std::string("[E::fcs-genome depth] fcsdp_count: ") + dp_api().last_error());
+      } else {
+        depth_count_host(view, prm_, w, depth.data(), host_threads());
+      }
+    }
+  }
+
+  void finish_window(size_t wi) {
+    const Window& win = windows_[wi];
+    const fcsdp_window& w = win.w;
+    std::vector<uint32_t> depth = std::move(open_[wi]);
+    open_.erase(wi);
+    if (depth.empty()) depth.assign((size_t)w.len, 0);
+    const std::string& seq = contigs_[(size_t)w.ref_id];
+    std::vector<uint64_t> bitmap((size_t)(w.len + 63) / 64, 0);
+    std::vector<fcsdp_piece> pieces;
+    for (const Part& p : win.parts) {
+      for (int64_t i = p.start; i < p.end; ++i) {
+        const char c = seq[(size_t)(w.start + i)];
+        if (include_ref_n_ || (c != 'N' && c != 'n')) bitmap[(size_t)(i >> 6)] |= (uint64_t)1 << (i & 63);
+      }
+      for (int64_t s = p.start; s < p.end; s += FCSDP_PIECE_MAX)
+        pieces.push_back({(int32_t)s, (int32_t)std::min<int64_t>(p.end, s + FCSDP_PIECE_MAX), long_index_[p.interval], 0});
+    }
+    std::vector<fcsdp_summary> sum(pieces.size());
+    if (device_ >= 0) {
+      if (dp_api().stats(device_, depth.data(), bitmap.data(), w.len, pieces.data(), (int64_t)pieces.size(), (int32_t)n_long_,
+                         hist_.data(), long_hist_.data(), sum.data()) != FCS_OK)
+        throw failedCommand(std::string("[E::fcs-genome depth] fcsdp_stats: ") + dp_api().last_error());
+    } else {
+      depth_stats_host(depth.data(), bitmap.data(), w.len, pieces.data(), (int64_t)pieces.size(), (int32_t)n_long_, hist_.data(),
+                       long_hist_.data(), sum.data(), host_threads());
+    }
+    size_t k = 0;
+    for (const Part& p : win.parts)
+      for (int64_t s = p.start; s < p.end; s += FCSDP_PIECE_MAX, ++k) {
+        DepthInterval& row = rows_[p.interval];
+        row.total += sum[k].total, row.loci += sum[k].loci, row.above += sum[k].above;
+        if (long_index_[p.interval] < 0) row.q1 = sum[k].q1, row.median = sum[k].median, row.q3 = sum[k].q3;
+        total_ += sum[k].total;
+      }
+    if (!job_.omit_base) {  // the per-locus text, formatted on the host pool piece by piece
+      constexpr int64_t kGroupLoci = 4 << 20;  // loci formatted at once: their text is what is held in memory
+      std::vector<std::string> text;
+      for (size_t g = 0; g < pieces.size();) {
+        size_t n = 0;
+        for (int64_t loci = 0; g + n < pieces.size() && loci < kGroupLoci; ++n) loci += pieces[g + n].end - pieces[g + n].start;
+        text.resize(std::max(text.size(), n));
+        parallel_tasks(n, host_threads(), [&](size_t i) {
+          text[i].clear();
+          depth_locus_lines(header_.names[(size_t)w.ref_id], w.start, depth.data(), bitmap.data(), pieces[g + i].start,
+                            pieces[g + i].end, text[i]);
+        });
+        for (size_t i = 0; i < n; ++i) locus_.write(text[i].data(), (std::streamsize)text[i].size());
+        g += n;
+      }
+    }
+  }
+
+  void write_files() {
+    for (size_t j = 0; j < intervals_.size(); ++j)
+      if (long_index_[j] >= 0) {
+        const uint64_t* h = long_hist_.data() + (size_t)long_index_[j] * FCSDP_BINS;
+        rows_[j].q1 = depth_quantile(h, 1), rows_[j].median = depth_quantile(h, 2), rows_[j].q3 = depth_quantile(h, 3);
+      }
+    const std::string& out = job_.output;
+    const std::string& sm = st_.sample;
+    if (!job_.omit_base) {
+      locus_.close();
+      if (!locus_) throw failedCommand("[E::fcs-genome depth] writing " + out + " failed");
+    }
+    if (!job_.omit_summary) {
+      write_file(out + ".sample_summary", depth_sample_summary_text(sm, hist_.data(), total_));
+      write_file(out + ".sample_statistics", depth_sample_statistics_text(sm, hist_.data()));
+    }
+    write_file(out + ".sample_cumulative_coverage_counts", depth_cumulative_counts_text(hist_.data()));
+    write_file(out + ".sample_cumulative_coverage_proportions", depth_cumulative_proportions_text(sm, hist_.data()));
+    if (!job_.omit_intervals) {
+      write_file(out + ".sample_interval_summary", depth_interval_summary_text(sm, rows_));
+      write_file(out + ".sample_interval_statistics", depth_interval_statistics_text(rows_));
+    }
+  }
+
+  const DepthJob& job_;
+  int device_;
+  std::vector<std::string> bams_;
+  std::unique_ptr<BamReader> reader_;
+  size_t file_ = 0, chunk_ = 1;
+  BamHeader header_;
+  std::vector<std::string> contigs_;
+  fcsdp_params prm_{};
+  bool include_ref_n_ = false;
+  int64_t window_bp_ = 1;
+  std::vector<Iv> intervals_;
+  std::vector<Window> windows_;
+  std::vector<DepthInterval> rows_;
+  std::vector<int32_t> long_index_;
+  size_t n_long_ = 0, cur_ = 0;
+  std::map<size_t, std::vector<uint32_t>> open_;
+  std::vector<uint64_t> hist_, long_hist_;
+  uint64_t total_ = 0;
+  std::pair<int64_t, int64_t> last_key_{-1, -1};
+  std::ofstream locus_;
+  DepthRunStats st_;
+};
+
+}  // namespace
+
+bool gpu_depth_available() {
+  const DpApi& a = dp_api();
+  return a.count && a.stats && a.last_error;
+}
+
+std::vector<std::string> depth_output_files(const DepthJob& job) {
+  std::vector<std::string> out;
+  if (!job.omit_base) out.push_back(job.output);
+  if (!job.omit_summary) out.push_back(job.output + ".sample_summary"), out.push_back(job.output + ".sample_statistics");
+  out.push_back(job.output + ".sample_cumulative_coverage_counts");
+  out.push_back(job.output + ".sample_cumulative_coverage_proportions");
+  if (!job.omit_intervals)
+    out.push_back(job.output + ".sample_interval_summary"), out.push_back(job.output + ".sample_interval_statistics");
+  return out;
+}
+
+DepthRunStats depth_run(const DepthJob& job) { return Run(job).run(); }
+
+}  // namespace fcsg

@@ -28,6 +28,7 @@
 #include "fcship.h"
 #include "aligner.h"
 #include "bqsr_run.h"
+#include "depth_run.h"
 #include "intervals.h"
 #include "markdup.h"
 #include "sample_sheet.h"
@@ -502,6 +503,53 @@ int bqsr_main(int argc, char** argv, BqsrCommand cmd) {
   return 0;
 }
 
+// `fcs-genome depth` (reference src/worker-depth.cpp:14-165, which runs GATK 3's
+// DepthOfCoverage per contig part and merges the parts' text files): the BAM
+// streams through host/depth_run.h in chunks over windows of the genome,
+// counted and summarised on the GPU (depth.gpu=true, include/fcsdp.h) or on
+// the host.  With depth.gpu=false the command needs no GPU.
+int depth_main(int argc, char** argv) {
+  Args a;
+  common_opts(a);
+  a.add("ref", "r", false, true, "reference genome path");
+  a.add("input", "i", false, true, "input BAM file or dir (coordinate-sorted)");
+  a.add("output", "o", false, true, "output coverage file (<output>.sample_* are written beside it)");
+  a.add("intervalList", "L", false, false, "Interval List BED File");
+  a.add("geneList", "g", false, false, "list of genes over which the coverage is calculated (refused: gene summaries are not built)");
+  a.add("sample-id", "", false, false, "sample tag for log files");
+  a.add("omitBaseOutput", "b", true, false, "omit output coverage depth at each base (default: false)");
+  a.add("omitIntervals", "v", true, false, "omit output coverage per-interval statistics (default false)");
+  a.add("omitSampleSummary", "s", true, false, "omit output summary files for each sample (default false)");
+  try {
+    a.parse(argc, argv);
+  } catch (helpRequest&) {
+    std::cerr << "'fcs-genome depth' options:\n" << a.help();
+    throw;
+  }
+  DepthJob job;
+  job.ref = a.get("ref"), job.input = a.get("input"), job.output = a.get("output");
+  if (a.has("intervalList")) job.intervals = a.get("intervalList");
+  if (a.has("sample-id")) (void)a.get("sample-id");
+  if (a.has("geneList")) {
+    (void)a.get("geneList");
+    throw invalidParam("--geneList: gene summaries are not built");
+  }
+  job.omit_base = a.has("omitBaseOutput"), job.omit_intervals = a.has("omitIntervals");
+  job.omit_summary = a.has("omitSampleSummary");
+  if (!is_regular_file(job.ref)) throw fileNotFound(job.ref);
+  if (!path_exists(job.input)) throw fileNotFound(job.input);
+  if (!job.intervals.empty() && !is_regular_file(job.intervals)) throw fileNotFound(job.intervals);
+  if (!a.has("force"))
+    for (const std::string& f : depth_output_files(job))
+      if (path_exists(f)) throw invalidParam("output " + f + " exists (use -f)");
+  if (conf().get_bool("depth.gpu")) job.device = slots().front();
+  const DepthRunStats st = depth_run(job);
+  std::cerr << "[fcs-genome depth] sample " << st.sample << ": " << st.records << " records, " << st.intervals << " intervals, "
+            << st.windows << " windows, " << st.loci << " loci, total depth " << st.total << ", " << st.seconds << " s ("
+            << (st.on_device ? "GPU" : "host") << ")" << std::endl;
+  return 0;
+}
+
 // `fcs-genome index -r ref.fasta`: the aligner's FMD-index, saved next to the
 // FASTA (<ref>.fcsidx) so that align maps it instead of building one per run
 // (bwa-flow reads the prebuilt bwa index; the reference expects it beside the
@@ -633,6 +681,7 @@ int print_help() {
                "  baserecal       base recalibration table of a BAM against known sites (GPU covariate counting)\n"
                "  printreads      apply a base recalibration table to a BAM (GPU table lookup)\n"
                "  bqsr            baserecal and printreads in one run\n"
+               "  depth           depth of coverage of a BAM per locus, interval and sample (GPU difference array + scan)\n"
                "  htc             variant calling, HaplotypeCaller-style (GPU PairHMM)\n"
                "  mutect2         somatic variant calling, tumor/normal (GPU PairHMM)\n"
                "  conf            print configuration keys\n"
@@ -676,6 +725,7 @@ int main(int argc, char** argv) {
     else if (cmd == "baserecal") ret = bqsr_main(argc - 1, argv + 1, BqsrCommand::kBaserecal);
     else if (cmd == "printreads" || cmd == "pr") ret = bqsr_main(argc - 1, argv + 1, BqsrCommand::kPrintreads);
     else if (cmd == "bqsr") ret = bqsr_main(argc - 1, argv + 1, BqsrCommand::kBqsr);
+    else if (cmd == "depth") ret = depth_main(argc - 1, argv + 1);
     else if (cmd == "synth") ret = synth_main(argc - 1, argv + 1);
     else if (cmd == "index") ret = index_main(argc - 1, argv + 1);
     else if (cmd == "conf") {
