@@ -968,3 +968,83 @@ def dp_stats(depth, bitmap, pieces, n_long=0, hist=None, long_hist=None, device:
     check(lib.fcsdp_stats(device, _ptr(depth), _ptr(bitmap), len(depth), _ptr(pc), len(pc), n_long, hist.ctypes.data,
                           _ptr(long_hist), _ptr(summary)))
     return hist, long_hist, summary
+
+
+# ---------------------------------------------------------------- pileup SNP genotyping (include/fcsug.h)
+UG_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "fcsug.h")
+FCSUG_TILE, FCSUG_WINDOW_MAX, FCSUG_TABLE_ROWS = 256, 1 << 24, 94
+FCSUG_STATUS_FIELD, FCSUG_STATUS_REF, FCSUG_STATUS_ORDER, FCSUG_STATUS_SITES = 1, 2, 4, 8
+
+
+class UgBatch(C.Structure):
+    _fields_ = DpBatch._fields_
+
+
+class UgParams(C.Structure):
+    _fields_ = [("min_baseq", C.c_int32)]
+
+
+class UgWindow(C.Structure):
+    _fields_ = DpWindow._fields_
+
+
+UG_SITE = np.dtype([("offset", np.int32), ("ref", np.uint8), ("alt", np.uint8), ("reserved", np.uint16),
+                    ("n", np.uint32, 4), ("qsum", np.uint32, 4), ("n_del", np.uint32), ("reserved2", np.uint32),
+                    ("mq2", np.uint64), ("gl", np.int64, 3)])
+
+_sig("fcsug_table", C.c_int, [C.c_double, C.c_void_p])
+_sig("fcsug_sites", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                              C.c_void_p])
+_sig("fcsug_workspace_bytes", C.c_int64, [C.c_int64, C.c_int64])
+_sig("fcsug_sites_dev", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                  C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])
+
+
+def ug_header_symbols() -> list[str]:
+    """Function names declared in include/fcsug.h."""
+    import re
+    txt = re.sub(r"/\*.*?\*/", "", open(UG_HEADER_PATH).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(fcsug_[a-z0-9_]+)\s*\(", txt)))
+
+
+_UG_DTYPES = (np.uint16, np.int32, np.int32, np.uint8, np.uint32, np.int64, np.uint8, np.uint8, np.int64, np.uint8)
+
+
+def ug_arrays(flag, ref_id, pos, mapq, cigar, cigar_off, bases, qual, base_off, qual_absent):
+    """The batch's arrays in the dtypes fcsug_batch names (bases: ASCII bytes)."""
+    return tuple(np.ascontiguousarray(a, t) for a, t in zip(
+        (flag, ref_id, pos, mapq, cigar, cigar_off, bases, qual, base_off, qual_absent), _UG_DTYPES))
+
+
+def ug_batch(arrays, n=None, n_cigar=None, n_bases=None) -> UgBatch:
+    """fcsug_batch over host arrays (ug_arrays' tuple, which the caller keeps alive)."""
+    flag, ref_id, pos, mapq, cigar, cigar_off, bases, qual, base_off, absent = arrays
+    return UgBatch(len(flag) if n is None else n, _ptr(flag), _ptr(ref_id), _ptr(pos), _ptr(mapq), _ptr(cigar),
+                   _ptr(cigar_off), len(cigar) if n_cigar is None else n_cigar, _ptr(bases), _ptr(qual), _ptr(base_off),
+                   len(qual) if n_bases is None else n_bases, _ptr(absent))
+
+
+def ug_table(pcr_error: float = 1e-4):
+    """fcsug_table: T[94][3] as int64."""
+    t = np.zeros((FCSUG_TABLE_ROWS, 3), np.int64)
+    check(lib.fcsug_table(pcr_error, t.ctypes.data))
+    return t
+
+
+def ug_sites(arrays, window, ref, table, min_baseq: int = 17, max_sites=None, device: int = 0, **kw):
+    """fcsug_sites: the sites (UG_SITE) of window = (ref_id, start, len, contig_len); ref: the window's len ASCII
+    reference bytes."""
+    arrays = ug_arrays(*arrays)
+    b = ug_batch(arrays, **kw)
+    ref_id, start, length, contig_len = window
+    w = UgWindow(ref_id, 0, start, length, contig_len)
+    prm = UgParams(min_baseq)
+    ref = np.frombuffer(ref.encode() if isinstance(ref, str) else bytes(ref), np.uint8)
+    assert len(ref) == length
+    table = np.ascontiguousarray(table, np.int64)
+    max_sites = length if max_sites is None else max_sites
+    sites = np.zeros(max(max_sites, 1), UG_SITE)
+    n = C.c_int64(-1)
+    check(lib.fcsug_sites(device, C.addressof(b), C.addressof(prm), C.addressof(w), _ptr(ref), _ptr(table), _ptr(sites),
+                          max_sites, C.addressof(n)))
+    return sites[:n.value]

@@ -13,6 +13,7 @@
 #include "bgzf.h"
 #include "bqsr.h"
 #include "depth.h"
+#include "ug.h"
 #include "common.h"
 #include "config.h"
 #include "executor.h"
@@ -573,6 +574,52 @@ int fcsg_depth_count(const fcsdp_batch* b, const fcsdp_params* prm, const fcsdp_
 int fcsg_depth_stats(const uint32_t* depth, const uint64_t* bitmap, int64_t len, const fcsdp_piece* pieces, int64_t n_pieces,
                      int32_t n_long, int threads, uint64_t* hist, uint64_t* long_hist, fcsdp_summary* summary) {
   return guard([&] { depth_stats_host(depth, bitmap, len, pieces, n_pieces, n_long, hist, long_hist, summary, threads); });
+}
+
+// The host statement of the pileup SNP model (ug.h) over a flat batch and a
+// window (include/fcsug.h): the table, the window's sites (at most max_sites
+// are written; the count is returned in *n_sites), and the VCF text of the
+// header and of the calls of sites, copied into buf[cap] (the length, or minus the size needed).
+int fcsg_ug_table(double pcr_error, int64_t* table) {
+  return guard([&] {
+    const std::vector<int64_t> t = ug_table(pcr_error);
+    std::copy(t.begin(), t.end(), table);
+  });
+}
+
+int fcsg_ug_sites(const fcsug_batch* b, const fcsug_params* prm, const fcsug_window* w, const uint8_t* ref, const int64_t* table,
+                  int threads, fcsug_site* sites, int64_t max_sites, int64_t* n_sites) {
+  return guard([&] {
+    const std::vector<fcsug_site> s = ug_sites_host(*b, *prm, *w, ref, table, threads);
+    if ((int64_t)s.size() > max_sites) throw failedCommand("[E::ug] the window has " + std::to_string(s.size()) + " sites, max_sites is " + std::to_string(max_sites));
+    std::copy(s.begin(), s.end(), sites);
+    *n_sites = (int64_t)s.size();
+  });
+}
+
+int fcsg_ug_vcf_text(const fcsug_site* sites, int64_t n, const char* chrom, int64_t window_start, double heterozygosity,
+                     double stand_call_conf, double max_deletion_fraction, char* buf, int cap) {
+  int rc = 0;
+  const int g = guard([&] {
+    UgGenotypeParams p;
+    p.heterozygosity = heterozygosity, p.stand_call_conf = stand_call_conf, p.max_deletion_fraction = max_deletion_fraction;
+    std::string out;
+    VcfRecord rec;
+    for (int64_t k = 0; k < n; ++k)
+      if (ug_genotype(sites[k], p, chrom, window_start, rec)) rec.append_line(out);
+    rc = copy_out(out, buf, cap);
+  });
+  return g ? g : rc;
+}
+
+int fcsg_ug_vcf_header(const char* sample, const char* names, const int64_t* lengths, char* buf, int cap) {
+  int rc = 0;
+  const int g = guard([&] {
+    std::vector<std::pair<std::string, int64_t>> contigs;
+    for (const std::string& name : split_lines(names)) contigs.emplace_back(name, lengths[contigs.size()]);
+    rc = copy_out(ug_vcf_header(sample, contigs).to_text(), buf, cap);
+  });
+  return g ? g : rc;
 }
 
 int fcsg_bam_index(const char* bam) {

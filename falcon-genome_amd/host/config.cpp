@@ -77,6 +77,14 @@ void Config::init(const std::string& root_dir) {
   declare("depth.max_baseq", "127", "depth: bases with a higher quality are not counted");
   declare("depth.include_deletions", "false", "depth: every deleted position adds 1");
   declare("depth.include_ref_n", "false", "depth: loci whose reference base is N take part");
+  declare("ug.gpu", "false", "pile sites up on the GPU (fcsug_sites) instead of on the host (ug)");
+  declare("ug.chunk_records", "1000000", "BAM records read at a time by ug");
+  declare("ug.window_bp", "1048576", "loci per window of ug at most (one device call each; DESIGN 4.12)");
+  declare("ug.min_baseq", "17", "ug: bases whose min(quality, MAPQ, 93) is lower are not counted");
+  declare("ug.stand_call_conf", "10", "ug: calls with a lower QUAL are not written");
+  declare("ug.heterozygosity", "0.001", "ug: the genotype prior's heterozygosity");
+  declare("ug.pcr_error", "0.0001", "ug: the PCR error rate folded into every base's error");
+  declare("ug.max_deletion_fraction", "0.05", "ug: sites where more than this fraction of the reads has a deletion are not called");
   // caller knobs (GATK HaplotypeCaller / Mutect2 argument defaults)
   declare("htc.min_base_quality", "10", "min base quality counted as evidence of activity");
   declare("htc.base_quality_threshold", "18", "PairHMM: base quals below this become 6");

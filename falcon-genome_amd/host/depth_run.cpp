@@ -61,67 +61,6 @@ int device_of(const DepthJob& job) {
 
 int host_threads() { return (int)std::min<unsigned>(host_cpus(), 16); }
 
-std::vector<std::string> input_bams(const std::string& input) {
-  if (is_regular_file(input)) return {input};
-  if (!is_directory(input)) throw fileNotFound(input);
-  std::vector<std::string> names = list_dir(input, ".bam");
-  std::sort(names.begin(), names.end());
-  std::vector<std::string> out;
-  for (const std::string& n : names) out.push_back(n.find('/') == std::string::npos ? input + "/" + n : n);
-  if (out.empty()) throw fileNotFound(input + "/*.bam");
-  return out;
-}
-
-// The single distinct SM of the header's @RG lines.
-std::string sample_of(const BamHeader& h) {
-  std::set<std::string> sm;
-  std::istringstream ss(h.text);
-  for (std::string line; std::getline(ss, line);) {
-    if (line.rfind("@RG", 0) != 0) continue;
-    for (size_t p = 0; p < line.size();) {
-      const size_t e = std::min(line.find('\t', p), line.size());
-      if (line.compare(p, 3, "SM:") == 0 && e > p + 3) sm.insert(line.substr(p + 3, e - p - 3));
-      p = e + 1;
-    }
-  }
-  if (sm.empty()) throw invalidParam("the BAM header names no sample (no @RG line with SM)");
-  if (sm.size() > 1) {
-    std::string all;
-    for (const std::string& s : sm) all += (all.empty() ? "" : ", ") + s;
-    throw invalidParam("the BAM header names " + std::to_string(sm.size()) + " samples (" + all + "); depth takes one");
-  }
-  return *sm.begin();
-}
-
-struct Iv {
-  int32_t ref;
-  int64_t start, end;  // 0-based half-open
-};
-
-// -L sorted by header contig order with overlapping and abutting intervals merged, or one interval per contig.
-std::vector<Iv> load_intervals(const std::string& path, const BamHeader& h) {
-  std::vector<Iv> iv;
-  if (path.empty()) {
-    for (size_t c = 0; c < h.names.size(); ++c) iv.push_back({(int32_t)c, 0, h.lengths[c]});
-    return iv;
-  }
-  for (const Interval& i : read_regions(path)) {
-    const int c = h.ref_index(i.chrom);
-    if (c < 0) throw invalidParam("contig " + i.chrom + " of " + path + " is not in the BAM header");
-    const int64_t s = std::max<int64_t>(i.lb - 1, 0), e = std::min<int64_t>(i.ub, h.lengths[(size_t)c]);
-    if (s >= e) throw invalidParam("interval " + i.chrom + ":" + std::to_string(i.lb) + "-" + std::to_string(i.ub) + " of " + path +
-                                   " is empty or beyond its contig");
-    iv.push_back({(int32_t)c, s, e});
-  }
-  std::sort(iv.begin(), iv.end(), [](const Iv& a, const Iv& b) { return a.ref != b.ref ? a.ref < b.ref : a.start < b.start; });
-  std::vector<Iv> out;
-  for (const Iv& i : iv) {
-    if (!out.empty() && out.back().ref == i.ref && i.start <= out.back().end) out.back().end = std::max(out.back().end, i.end);
-    else out.push_back(i);
-  }
-  return out;
-}
-
 struct Part {
   size_t interval;
   int64_t start, end;  // window offsets
@@ -181,10 +120,10 @@ std::pair<int64_t, int64_t> key_of(int32_t ref_id, int32_t pos) { return {ref_id
 
 class Run {
  public:
-  explicit Run(const DepthJob& job) : job_(job), device_(device_of(job)), bams_(input_bams(job.input)) {
+  explicit Run(const DepthJob& job) : job_(job), device_(device_of(job)), bams_(sorted_bam_inputs(job.input)) {
     reader_.reset(new BamReader(bams_[0]));
     header_ = reader_->header();
-    st_.sample = sample_of(header_);
+    st_.sample = single_sample(header_, "depth");
     const Reference ref = load_fasta(job.ref);
     contigs_.resize(header_.names.size());
     for (size_t k = 0; k < header_.names.size(); ++k) {
@@ -204,7 +143,7 @@ class Run {
     include_ref_n_ = cf.get_bool("depth.include_ref_n");
     chunk_ = (size_t)std::max(cf.get_int("depth.chunk_records"), 1);
     window_bp_ = std::clamp<int64_t>(cf.get_int("depth.window_bp"), 1, FCSDP_WINDOW_MAX);
-    intervals_ = load_intervals(job.intervals, header_);
+    intervals_ = merged_intervals(job.intervals, header_);
     cut_windows();
     hist_.assign(FCSDP_BINS, 0);
     long_hist_.assign((size_t)FCSDP_BINS * n_long_, 0);
@@ -277,7 +216,7 @@ class Run {
     for (const Window& w : windows_)
       for (const Part& p : w.parts) ++n_parts[p.interval];
     for (size_t j = 0; j < intervals_.size(); ++j) {
-      const Iv& i = intervals_[j];
+      const GenomeInterval& i = intervals_[j];
       if (n_parts[j] > 1 || i.end - i.start > FCSDP_PIECE_MAX) long_index_[j] = n_long_++;
       rows_[j].name = header_.names[(size_t)i.ref] + ":" + std::to_string(i.start + 1) +
                       (i.end - i.start > 1 ? "-" + std::to_string(i.end) : "");
@@ -433,7 +372,7 @@ class Run {
   fcsdp_params prm_{};
   bool include_ref_n_ = false;
   int64_t window_bp_ = 1;
-  std::vector<Iv> intervals_;
+  std::vector<GenomeInterval> intervals_;
   std::vector<Window> windows_;
   std::vector<DepthInterval> rows_;
   std::vector<int32_t> long_index_;
@@ -447,6 +386,62 @@ class Run {
 };
 
 }  // namespace
+
+std::vector<std::string> sorted_bam_inputs(const std::string& input) {
+  if (is_regular_file(input)) return {input};
+  if (!is_directory(input)) throw fileNotFound(input);
+  std::vector<std::string> names = list_dir(input, ".bam");
+  std::sort(names.begin(), names.end());
+  std::vector<std::string> out;
+  for (const std::string& n : names) out.push_back(n.find('/') == std::string::npos ? input + "/" + n : n);
+  if (out.empty()) throw fileNotFound(input + "/*.bam");
+  return out;
+}
+
+// The single distinct SM of the header's @RG lines.
+std::string single_sample(const BamHeader& h, const std::string& command) {
+  std::set<std::string> sm;
+  std::istringstream ss(h.text);
+  for (std::string line; std::getline(ss, line);) {
+    if (line.rfind("@RG", 0) != 0) continue;
+    for (size_t p = 0; p < line.size();) {
+      const size_t e = std::min(line.find('\t', p), line.size());
+      if (line.compare(p, 3, "SM:") == 0 && e > p + 3) sm.insert(line.substr(p + 3, e - p - 3));
+      p = e + 1;
+    }
+  }
+  if (sm.empty()) throw invalidParam("the BAM header names no sample (no @RG line with SM)");
+  if (sm.size() > 1) {
+    std::string all;
+    for (const std::string& s : sm) all += (all.empty() ? "" : ", ") + s;
+    throw invalidParam("the BAM header names " + std::to_string(sm.size()) + " samples (" + all + "); " + command + " takes one");
+  }
+  return *sm.begin();
+}
+
+// -L sorted by header contig order with overlapping and abutting intervals merged, or one interval per contig.
+std::vector<GenomeInterval> merged_intervals(const std::string& path, const BamHeader& h) {
+  std::vector<GenomeInterval> iv;
+  if (path.empty()) {
+    for (size_t c = 0; c < h.names.size(); ++c) iv.push_back({(int32_t)c, 0, h.lengths[c]});
+    return iv;
+  }
+  for (const Interval& i : read_regions(path)) {
+    const int c = h.ref_index(i.chrom);
+    if (c < 0) throw invalidParam("contig " + i.chrom + " of " + path + " is not in the BAM header");
+    const int64_t s = std::max<int64_t>(i.lb - 1, 0), e = std::min<int64_t>(i.ub, h.lengths[(size_t)c]);
+    if (s >= e) throw invalidParam("interval " + i.chrom + ":" + std::to_string(i.lb) + "-" + std::to_string(i.ub) + " of " + path +
+                                   " is empty or beyond its contig");
+    iv.push_back({(int32_t)c, s, e});
+  }
+  std::sort(iv.begin(), iv.end(), [](const GenomeInterval& a, const GenomeInterval& b) { return a.ref != b.ref ? a.ref < b.ref : a.start < b.start; });
+  std::vector<GenomeInterval> out;
+  for (const GenomeInterval& i : iv) {
+    if (!out.empty() && out.back().ref == i.ref && i.start <= out.back().end) out.back().end = std::max(out.back().end, i.end);
+    else out.push_back(i);
+  }
+  return out;
+}
 
 bool gpu_depth_available() {
   const DpApi& a = dp_api();

@@ -9,6 +9,20 @@
 
 namespace fcsg {
 
+struct BamHeader;
+
+// What the commands that stream one sorted BAM over windows of the genome share (depth, ug).
+// The input BAM, or the part BAMs of a directory in name order.
+std::vector<std::string> sorted_bam_inputs(const std::string& input);
+// The single distinct SM of the header's @RG lines; invalidParam without one or with several.
+std::string single_sample(const BamHeader& h, const std::string& command);
+struct GenomeInterval {
+  int32_t ref;
+  int64_t start, end;  // 0-based half-open
+};
+// -L sorted by header contig order with overlapping and abutting intervals merged, or one interval per contig.
+std::vector<GenomeInterval> merged_intervals(const std::string& path, const BamHeader& h);
+
 struct DepthJob {
   std::string ref;        // FASTA
   std::string input;      // a coordinate-sorted BAM, or a directory whose part BAMs in name order form one

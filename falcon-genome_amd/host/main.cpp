@@ -29,6 +29,7 @@
 #include "aligner.h"
 #include "bqsr_run.h"
 #include "depth_run.h"
+#include "ug_run.h"
 #include "intervals.h"
 #include "markdup.h"
 #include "sample_sheet.h"
@@ -550,6 +551,48 @@ int depth_main(int argc, char** argv) {
   return 0;
 }
 
+// `fcs-genome ug` (reference src/worker-ug.cpp, src/workers/UGWorker.cpp, which
+// run GATK 3's UnifiedGenotyper per shard and concatenate the shards' VCFs): the
+// BAM streams through host/ug_run.h in chunks gathered per window of the
+// genome, piled up on the GPU (ug.gpu=true, include/fcsug.h) or on the host and
+// genotyped by the SNP model.  With ug.gpu=false the command needs no GPU.
+int ug_main(int argc, char** argv) {
+  Args a;
+  common_opts(a);
+  a.add("ref", "r", false, true, "reference genome path");
+  a.add("input", "i", false, true, "input BAM file or dir (coordinate-sorted)");
+  a.add("output", "o", false, true, "output VCF file (<output>.gz and <output>.gz.tbi are written beside it)");
+  a.add("intervalList", "L", false, false, "Interval List BED File");
+  a.add("sample-id", "", false, false, "sample tag for log files");
+  a.add("skip-concat", "s", true, false, "produce a set of VCF files instead of one (refused: one run is one stream)");
+  a.add("extra-options", "O", false, false, "extra options for GATK (accepted and ignored)");
+  try {
+    a.parse(argc, argv);
+  } catch (helpRequest&) {
+    std::cerr << "'fcs-genome ug' options:\n" << a.help();
+    throw;
+  }
+  UgJob job;
+  job.ref = a.get("ref"), job.input = a.get("input"), job.output = a.get("output");
+  if (a.has("intervalList")) job.intervals = a.get("intervalList");
+  if (a.has("sample-id")) (void)a.get("sample-id");
+  if (a.has("skip-concat")) throw invalidParam("--skip-concat: one run is one stream and writes one VCF, there are no parts to keep");
+  if (a.has("extra-options"))
+    std::cerr << "[fcs-genome ug] --extra-options " << a.get("extra-options") << ": ignored (no GATK is run)" << std::endl;
+  if (!is_regular_file(job.ref)) throw fileNotFound(job.ref);
+  if (!path_exists(job.input)) throw fileNotFound(job.input);
+  if (!job.intervals.empty() && !is_regular_file(job.intervals)) throw fileNotFound(job.intervals);
+  if (!a.has("force"))
+    for (const std::string& f : ug_output_files(job))
+      if (path_exists(f)) throw invalidParam("output " + f + " exists (use -f)");
+  if (conf().get_bool("ug.gpu")) job.device = slots().front();
+  const UgRunStats st = ug_run(job);
+  std::cerr << "[fcs-genome ug] sample " << st.sample << ": " << st.records << " records, " << st.intervals << " intervals, "
+            << st.windows << " windows, " << st.sites << " sites, " << st.calls << " calls, " << st.seconds << " s ("
+            << (st.on_device ? "GPU" : "host") << ")" << std::endl;
+  return 0;
+}
+
 // `fcs-genome index -r ref.fasta`: the aligner's FMD-index, saved next to the
 // FASTA (<ref>.fcsidx) so that align maps it instead of building one per run
 // (bwa-flow reads the prebuilt bwa index; the reference expects it beside the
@@ -682,6 +725,7 @@ int print_help() {
                "  printreads      apply a base recalibration table to a BAM (GPU table lookup)\n"
                "  bqsr            baserecal and printreads in one run\n"
                "  depth           depth of coverage of a BAM per locus, interval and sample (GPU difference array + scan)\n"
+               "  ug              SNP calling from the pileup, UnifiedGenotyper-style (GPU pileup in LDS tiles)\n"
                "  htc             variant calling, HaplotypeCaller-style (GPU PairHMM)\n"
                "  mutect2         somatic variant calling, tumor/normal (GPU PairHMM)\n"
                "  conf            print configuration keys\n"
@@ -726,6 +770,7 @@ int main(int argc, char** argv) {
     else if (cmd == "printreads" || cmd == "pr") ret = bqsr_main(argc - 1, argv + 1, BqsrCommand::kPrintreads);
     else if (cmd == "bqsr") ret = bqsr_main(argc - 1, argv + 1, BqsrCommand::kBqsr);
     else if (cmd == "depth") ret = depth_main(argc - 1, argv + 1);
+    else if (cmd == "ug" || cmd == "unifiedgeno") ret = ug_main(argc - 1, argv + 1);
     else if (cmd == "synth") ret = synth_main(argc - 1, argv + 1);
     else if (cmd == "index") ret = index_main(argc - 1, argv + 1);
     else if (cmd == "conf") {

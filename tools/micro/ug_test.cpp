@@ -1,0 +1,237 @@
+// Host check of csrc/ug_pile.h (the text the gfx950 kernels of csrc/ug.hip
+// run): random sorted batches go through the header's functions the way the
+// kernels call them (the record filter and span, then per tile of 256 loci a
+// record in passes of 64 lanes: each lane's locus, letter and effective
+// quality added to the tile's cells, the D ops, then a lane per locus: the site
+// predicate, the alt choice and the gl sums) and every site is compared with
+// host/ug.cpp, which states the rules with plain loops, on 1 and on 4 threads.
+//   g++ -O1 -std=c++17 -pthread -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+//       -Iinclude -Ifalcon-genome_amd/csrc -Ifalcon-genome_amd/host tools/micro/ug_test.cpp \
+//       falcon-genome_amd/host/ug.cpp -o ug_test
+//   ug_test [SEED [RECORDS]]
+// Prints the batch's figures and "ok", or MISMATCH lines and exit status 1.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <numeric>
+#include <random>
+#include <vector>
+
+#include "ug.h"
+#include "ug_pile.h"
+
+using namespace fcsg;
+using namespace fcs;
+
+namespace {
+
+constexpr int64_t kContig = 6000;
+constexpr int kTile = FCSUG_TILE;
+
+struct Record {
+  uint16_t flag;
+  int32_t ref_id, pos;
+  uint8_t mapq, absent;
+  std::vector<uint32_t> cigar;
+  std::vector<uint8_t> bases, qual;
+};
+
+struct Batch {
+  std::vector<uint16_t> flag;
+  std::vector<int32_t> ref_id, pos;
+  std::vector<uint8_t> mapq, absent, qual, bases;
+  std::vector<uint32_t> cigar;
+  std::vector<int64_t> cigar_off{0}, base_off{0};
+  fcsug_batch view() const {
+    fcsug_batch b;
+    b.n = (int64_t)flag.size();
+    b.flag = flag.data(), b.ref_id = ref_id.data(), b.pos = pos.data(), b.mapq = mapq.data();
+    b.cigar = cigar.data(), b.cigar_off = cigar_off.data(), b.n_cigar = (int64_t)cigar.size();
+    b.bases = bases.data(), b.qual = qual.data(), b.base_off = base_off.data(), b.n_bases = (int64_t)qual.size();
+    b.qual_absent = absent.data();
+    return b;
+  }
+};
+
+Record make_record(std::mt19937_64& rnd, const std::vector<uint8_t>* refs) {
+  static const int lengths[] = {1, 2, 15, 63, 64, 65, 127, 128, 129, 151, 151, 200};
+  static const uint8_t quals[] = {2, 5, 16, 17, 18, 25, 30, 31, 37, 40, 41, 93};
+  static const uint16_t flags[] = {0, 0, 0, 0x10, 0x41, 0x91, 0x800, 0x4, 0x100, 0x200, 0x400};
+  static const uint8_t mapqs[] = {0, 16, 17, 30, 60, 60, 255};
+  Record r;
+  int left = lengths[rnd() % 12];
+  r.pos = (int32_t)(rnd() % (kContig - 900));
+  r.ref_id = (int32_t)(rnd() % 2);
+  if (rnd() % 10 == 0) r.cigar.push_back((5u << 4) | 5u);
+  if (left > 12 && rnd() % 4 == 0) {
+    const int lead = (int)(rnd() % 9) + 1;
+    r.cigar.push_back(((uint32_t)lead << 4) | 4u);
+    left -= lead;
+  }
+  const int trail = left > 12 && rnd() % 4 == 0 ? (int)(rnd() % 7) + 1 : 0;
+  left -= trail;
+  bool first = true;
+  int gaps = 0;
+  while (left > 0) {
+    if (!first && gaps++ < 8) {  // at most 8 gaps: the span stays inside the contig
+      const unsigned gap = (unsigned)(rnd() % 10);
+      if (gap < 3) r.cigar.push_back(((uint32_t)(1 + rnd() % 5) << 4) | 2u);
+      else if (gap < 4) r.cigar.push_back(((uint32_t)(1 + rnd() % 40) << 4) | 3u);
+      else if (gap < 5) r.cigar.push_back((1u << 4) | 6u);
+      else if (gap < 8 && left > 1) {
+        const int n = 1 + (int)(rnd() % (unsigned)std::min(left - 1, 7));
+        r.cigar.push_back(((uint32_t)n << 4) | 1u);
+        left -= n;
+      }
+    }
+    const int n = rnd() % 2 ? left : 1 + (int)(rnd() % (unsigned)left);
+    static const uint32_t mops[] = {0, 0, 0, 7, 8};
+    r.cigar.push_back(((uint32_t)n << 4) | mops[rnd() % 5]);
+    left -= n;
+    first = false;
+  }
+  if (trail) r.cigar.push_back(((uint32_t)trail << 4) | 4u);
+  r.absent = rnd() % 30 == 0;
+  // the read: the reference's letters along the CIGAR, one base in 20 replaced (some by N or a lower-case letter)
+  int64_t p = r.pos;
+  for (uint32_t word : r.cigar) {
+    const uint32_t op = word & 15u, len = word >> 4;
+    for (uint32_t j = 0; j < len && (op == 0 || op == 1 || op == 4 || op == 7 || op == 8); ++j) {
+      uint8_t c = op == 1 || op == 4 ? 'A' : refs[r.ref_id][(size_t)(p + j)];
+      if (rnd() % 20 == 0) c = (uint8_t) "ACGTNacgt"[rnd() % 9];
+      r.bases.push_back(c);
+      r.qual.push_back(r.absent ? 0xff : quals[rnd() % 12]);
+    }
+    if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) p += len;
+  }
+  r.flag = flags[rnd() % 11];
+  r.mapq = mapqs[rnd() % 7];
+  return r;
+}
+
+struct Cell {
+  uint32_t n[4] = {0, 0, 0, 0}, qsum[4] = {0, 0, 0, 0}, n_del = 0;
+  uint64_t mq2 = 0;
+  int64_t A[4] = {0, 0, 0, 0}, B[4] = {0, 0, 0, 0}, C[4] = {0, 0, 0, 0};
+};
+
+// ug_span_kernel's filter, then ug_tile_kernel tile by tile, lane by lane.
+std::vector<fcsug_site> sites_shared(const fcsug_batch& b, const fcsug_params& prm, const fcsug_window& w, const uint8_t* ref,
+                                     const int64_t* table, int64_t& counted_bases) {
+  std::vector<int64_t> end((size_t)b.n, INT64_MIN);
+  for (int64_t r = 0; r < b.n; ++r) {
+    if (b.ref_id[r] != w.ref_id) continue;
+    const int64_t n_ops = b.cigar_off[r + 1] - b.cigar_off[r];
+    if (!ug_counted(b.flag[r], b.ref_id[r], n_ops, b.mapq[r])) continue;
+    int64_t covered, ref_len;
+    bool beyond;
+    ug_span(b.cigar + b.cigar_off[r], n_ops, b.pos[r], w.contig_len, covered, ref_len, beyond);
+    if (covered == b.base_off[r + 1] - b.base_off[r]) end[(size_t)r] = b.pos[r] + ref_len;
+  }
+  std::vector<fcsug_site> out;
+  for (int64_t t = 0; t * kTile < w.len; ++t) {
+    const int64_t s = w.start + t * kTile, e = std::min(s + kTile, w.start + w.len);
+    Cell cells[kTile];
+    for (int64_t r = 0; r < b.n; ++r) {
+      if (end[(size_t)r] == INT64_MIN || end[(size_t)r] <= s || b.pos[r] >= e) continue;
+      const uint32_t* cigar = b.cigar + b.cigar_off[r];
+      const int64_t n_ops = b.cigar_off[r + 1] - b.cigar_off[r], L = b.base_off[r + 1] - b.base_off[r];
+      const int mapq = b.mapq[r];
+      for (int64_t i0 = 0; i0 < L; i0 += 64)
+        for (int lane = 0; lane < 64; ++lane) {
+          const int64_t i = i0 + lane;
+          int64_t p;
+          if (!(i < L && ug_locus(cigar, n_ops, b.pos[r], i, p) && p >= s && p < e)) continue;
+          const int x = ug_code(b.bases[b.base_off[r] + i]);
+          const int qe = ug_qe(b.qual_absent[r] ? 0 : b.qual[b.base_off[r] + i], mapq);
+          if (x > 3 || qe < prm.min_baseq) continue;
+          Cell& c = cells[p - s];
+          ++c.n[x], c.qsum[x] += (uint32_t)qe, c.mq2 += (uint64_t)(mapq * mapq), ++counted_bases;
+          c.A[x] += table[3 * qe], c.B[x] += table[3 * qe + 1], c.C[x] += table[3 * qe + 2];
+        }
+      if (ug_qe(kUgMaxQ, mapq) < prm.min_baseq) continue;
+      int64_t p = b.pos[r];
+      for (int64_t k = 0; k < n_ops; ++k) {
+        const uint32_t op = cigar[k] & 15u;
+        const int64_t len = cigar[k] >> 4;
+        if (op == 2u)
+          for (int64_t j = std::max(p, s); j < std::min(p + len, e); ++j) ++cells[j - s].n_del;
+        if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) p += len;
+      }
+    }
+    for (int64_t i = 0; s + i < e; ++i) {
+      const Cell& c = cells[i];
+      const int rc = ug_code(ref[t * kTile + i]);
+      if (!ug_is_site(rc, c.n)) continue;
+      fcsug_site o{};
+      o.offset = (int32_t)(t * kTile + i), o.ref = (uint8_t)rc, o.alt = (uint8_t)ug_alt(rc, c.qsum);
+      for (int x = 0; x < 4; ++x) o.n[x] = c.n[x], o.qsum[x] = c.qsum[x];
+      o.n_del = c.n_del, o.mq2 = c.mq2;
+      ug_gl(rc, o.alt, c.A, c.B, c.C, o.gl);
+      out.push_back(o);
+    }
+  }
+  return out;
+}
+
+bool same(const fcsug_site& a, const fcsug_site& b) { return std::memcmp(&a, &b, sizeof a) == 0; }
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  const uint64_t seed = argc > 1 ? std::strtoull(argv[1], nullptr, 10) : 1;
+  const int n = argc > 2 ? std::atoi(argv[2]) : 3000;
+  std::mt19937_64 rnd(seed);
+  std::vector<uint8_t> refs[2];
+  for (auto& ref : refs) {
+    for (int64_t i = 0; i < kContig; ++i) ref.push_back((uint8_t) "ACGT"[rnd() % 4]);
+    for (int64_t i = 1000; i < 1100; ++i) ref[(size_t)i] = 'N';
+    for (int64_t i = 2000; i < 2300; ++i) ref[(size_t)i] |= 0x20;  // lower case
+  }
+  std::vector<Record> recs;
+  for (int r = 0; r < n; ++r) recs.push_back(make_record(rnd, refs));
+  std::stable_sort(recs.begin(), recs.end(), [](const Record& a, const Record& b) { return a.pos < b.pos; });
+  Batch batch;
+  for (const Record& r : recs) {
+    batch.flag.push_back(r.flag), batch.ref_id.push_back(r.ref_id), batch.pos.push_back(r.pos), batch.mapq.push_back(r.mapq);
+    batch.absent.push_back(r.absent);
+    batch.cigar.insert(batch.cigar.end(), r.cigar.begin(), r.cigar.end());
+    batch.bases.insert(batch.bases.end(), r.bases.begin(), r.bases.end());
+    batch.qual.insert(batch.qual.end(), r.qual.begin(), r.qual.end());
+    batch.cigar_off.push_back((int64_t)batch.cigar.size()), batch.base_off.push_back((int64_t)batch.qual.size());
+  }
+  const fcsug_batch b = batch.view();
+  const std::vector<int64_t> table = ug_table(1e-4);
+  int bad = 0;
+  int64_t counted_bases = 0, n_sites = 0, calls = 0;
+  const fcsug_params prms[] = {{17}, {0}, {31}};
+  const fcsug_window windows[] = {{0, 0, 0, kContig, kContig}, {1, 0, 1000, 4096, kContig}, {0, 0, 255, 258, kContig},
+                                  {1, 0, kContig - 1, 1, kContig}};
+  for (const fcsug_params& prm : prms)
+    for (const fcsug_window& w : windows) {
+      const uint8_t* ref = refs[w.ref_id].data() + w.start;
+      const std::vector<fcsug_site> want = ug_sites_host(b, prm, w, ref, table.data(), 1);
+      const std::vector<fcsug_site> want4 = ug_sites_host(b, prm, w, ref, table.data(), 4);
+      const std::vector<fcsug_site> got = sites_shared(b, prm, w, ref, table.data(), counted_bases);
+      n_sites += (int64_t)want.size();
+      if (want.size() != got.size() || want.size() != want4.size()) {
+        if (bad++ < 10)
+          std::printf("MISMATCH site count of window %lld+%lld: host %zu (4 threads %zu), shared %zu\n", (long long)w.start,
+                      (long long)w.len, want.size(), want4.size(), got.size());
+        continue;
+      }
+      VcfRecord rec;
+      for (size_t k = 0; k < want.size(); ++k) {
+        if ((!same(want[k], got[k]) || !same(want[k], want4[k])) && bad++ < 10)
+          std::printf("MISMATCH site %zu at offset %d of window %lld+%lld (shared offset %d)\n", k, want[k].offset,
+                      (long long)w.start, (long long)w.len, got[k].offset);
+        calls += ug_genotype(got[k], UgGenotypeParams{}, "c", w.start, rec);
+      }
+    }
+  std::printf("records %d counted_bases %lld sites %lld calls %lld\n", n, (long long)counted_bases, (long long)n_sites,
+              (long long)calls);
+  if (bad) return 1;
+  std::printf("ok\n");
+  return 0;
+}
