@@ -46,6 +46,7 @@
 #include "bq_covars.h"
 #include "fcsbq.h"
 #include "fcship_internal.h"
+#include "rec_batch.h"
 
 struct fcsbq_ref {
   int32_t device = 0;
@@ -71,8 +72,6 @@ struct BqDevRef {
   const uint64_t* known;
   int32_t n_ref;
 };
-
-__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 // The low-quality ends of qual[0, k), k <= 500, found by the whole wave.
 __device__ __forceinline__ void wave_low_ends(const uint8_t* qual, int64_t k, int lane, int64_t& nl, int64_t& nr) {
@@ -110,6 +109,7 @@ __global__ __launch_bounds__(kBqBlock) void bq_count_kernel(fcsbq_batch b, BqDev
       if (bad && lane == 0) atomicOr(status, bad);
       continue;
     }
+    // rec_fields' ranges in this kernel's own order (bases first): the shared order changes its machine code
     const int64_t o0 = b.base_off[r], o1 = b.base_off[r + 1];
     const int64_t q0 = clamp64(o0, 0, b.n_bases), q1 = clamp64(o1, q0, b.n_bases);
     const int64_t k0 = b.cigar_off[r], k1 = b.cigar_off[r + 1];
@@ -227,8 +227,6 @@ __global__ __launch_bounds__(kBqBlock) void bq_apply_kernel(fcsbq_batch b, int32
   }
 }
 
-int bq_fail(const char* who, const std::string& what) { return fail(FCS_ERR_INVALID, std::string("[E::") + who + "] " + what); }
-
 // Replicas of the count table: 16 (1, 4, 8 and 16 were measured,
 // each step faster), fewer when the read groups are many (64 MiB of replicas
 // at most); FCS_BQ_REPLICAS (1 .. 64) sets it for measurements.
@@ -279,39 +277,27 @@ int launch_apply(const fcsbq_batch& b, int32_t n_rg, const double* base, const d
   return FCS_OK;
 }
 
-// The scalar fields of a batch, checked alike by every entry point.
+// The scalar fields of a batch, checked alike by every entry point: the shared
+// check, with the two limits of this file where they have always stood, after
+// its refusals of a null batch and of negative sizes.
 int check_scalars(const fcsbq_batch* b, int32_t n_rg, const char* who) {
-  if (!b) return bq_fail(who, "null batch");
-  if (b->n < 0) return bq_fail(who, "negative record count " + std::to_string(b->n));
-  if (b->n_cigar < 0 || b->n_bases < 0) return bq_fail(who, "negative CIGAR or base size");
-  if (b->n_bases > FCSBQ_MAX_BASES)
-    return bq_fail(who, std::to_string(b->n_bases) + " bases: a call holds fewer than 2^32");
-  if (n_rg < 0 || n_rg > FCSBQ_MAX_RG)
-    return bq_fail(who, std::to_string(n_rg) + " read groups (at most " + std::to_string(FCSBQ_MAX_RG) + ")");
-  if (b->n > 0 && (!b->flag || !b->ref_id || !b->pos || !b->mapq || !b->rg || !b->cigar_off || !b->base_off || !b->qual_absent))
-    return bq_fail(who, "null array");
-  if ((b->n_cigar > 0 && !b->cigar) || (b->n_bases > 0 && (!b->bases || !b->qual))) return bq_fail(who, "null CIGAR, base or quality bytes");
-  return FCS_OK;
+  if (b && b->n >= 0 && b->n_cigar >= 0 && b->n_bases >= 0) {
+    if (b->n_bases > FCSBQ_MAX_BASES)
+      return fail_invalid(who, std::to_string(b->n_bases) + " bases: a call holds fewer than 2^32");
+    if (n_rg < 0 || n_rg > FCSBQ_MAX_RG)
+      return fail_invalid(who, std::to_string(n_rg) + " read groups (at most " + std::to_string(FCSBQ_MAX_RG) + ")");
+  }
+  return check_batch_scalars(b, true, who);
 }
 
 // Every offset and read group of a batch of host arrays.
 int check_arrays(const fcsbq_batch* b, int32_t n_rg, const char* who) {
-  const int64_t n = b->n;
-  for (int k = 0; k < 2; ++k) {
-    const int64_t* off = k ? b->base_off : b->cigar_off;
-    const int64_t total = k ? b->n_bases : b->n_cigar;
-    const char* what = k ? "base" : "CIGAR";
-    if (n > 0 && off[0] < 0) return bq_fail(who, std::string(what) + " offsets start below zero");
-    for (int64_t r = 0; r < n; ++r)
-      if (off[r + 1] < off[r]) return bq_fail(who, std::string(what) + " offsets out of order at record " + std::to_string(r));
-    if (n > 0 && off[n] > total)
-      return bq_fail(who, std::string(what) + " offsets end at " + std::to_string(off[n]) + ", beyond the " +
-                              std::to_string(total) + " given");
-  }
-  for (int64_t r = 0; r < n; ++r)
+  const int rc = check_batch_offsets(b, who);
+  if (rc) return rc;
+  for (int64_t r = 0; r < b->n; ++r)
     if (b->rg[r] < -1 || b->rg[r] >= n_rg)
-      return bq_fail(who, "read group " + std::to_string(b->rg[r]) + " of record " + std::to_string(r) + " is outside [-1, " +
-                              std::to_string(n_rg) + ")");
+      return fail_invalid(who, "read group " + std::to_string(b->rg[r]) + " of record " + std::to_string(r) + " is outside [-1, " +
+                                        std::to_string(n_rg) + ")");
   return FCS_OK;
 }
 
@@ -326,66 +312,27 @@ const fcsbq_ref* live_ref(const fcsbq_ref* h, const char* who) {
     std::lock_guard<std::mutex> lk(g_ref_mu);
     if (live_refs().count(h)) return h;
   }
-  bq_fail(who, h ? "the reference handle is not a live one" : "null reference handle");
+  fail_invalid(who, h ? "the reference handle is not a live one" : "null reference handle");
   return nullptr;
 }
 
-// The sizes and places of a batch's arrays in a session's arenas.
+// The shared layout and stage with the read groups, which only these batches hold, behind them.
 struct BqLayout {
-  size_t flag, ref_id, pos, mapq, rg, absent, coff, boff, cigar, bases, qual, in_bytes;
+  BatchLayout batch;
+  size_t rg;
 };
 
-size_t pad256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-BqLayout layout_of(const fcsbq_batch& b, size_t& total) {
-  const size_t N = (size_t)b.n, nc = (size_t)b.cigar_off[b.n], nb = (size_t)b.base_off[b.n];
-  auto add = [&](size_t bytes) {
-    const size_t o = total;
-    total += pad256(bytes);
-    return o;
-  };
-  BqLayout l;
-  l.flag = add(2 * N), l.ref_id = add(4 * N), l.pos = add(4 * N), l.mapq = add(N), l.rg = add(4 * N), l.absent = add(N);
-  l.coff = add(8 * (N + 1)), l.boff = add(8 * (N + 1)), l.cigar = add(4 * nc), l.bases = add(nb), l.qual = add(nb);
-  l.in_bytes = total;
-  return l;
+BqLayout layout_of(const fcsbq_batch& b, Arena& a) {
+  const BatchLayout l = layout_batch(b, true, a);
+  return BqLayout{l, a.add(4 * (size_t)b.n)};
 }
 
-// Copies the batch into the host arena and answers its device view.
 fcsbq_batch stage(const fcsbq_batch& b, const BqLayout& l, char* host, char* dev) {
-  const size_t N = (size_t)b.n, nc = (size_t)b.cigar_off[b.n], nb = (size_t)b.base_off[b.n];
-  std::memcpy(host + l.flag, b.flag, 2 * N);
-  std::memcpy(host + l.ref_id, b.ref_id, 4 * N);
-  std::memcpy(host + l.pos, b.pos, 4 * N);
-  std::memcpy(host + l.mapq, b.mapq, N);
-  std::memcpy(host + l.rg, b.rg, 4 * N);
-  std::memcpy(host + l.absent, b.qual_absent, N);
-  std::memcpy(host + l.coff, b.cigar_off, 8 * (N + 1));
-  std::memcpy(host + l.boff, b.base_off, 8 * (N + 1));
-  if (nc) std::memcpy(host + l.cigar, b.cigar, 4 * nc);
-  if (nb) std::memcpy(host + l.bases, b.bases, nb), std::memcpy(host + l.qual, b.qual, nb);
-  fcsbq_batch d;
-  d.n = b.n;
-  d.flag = reinterpret_cast<const uint16_t*>(dev + l.flag);
-  d.ref_id = reinterpret_cast<const int32_t*>(dev + l.ref_id);
-  d.pos = reinterpret_cast<const int32_t*>(dev + l.pos);
-  d.mapq = reinterpret_cast<const uint8_t*>(dev + l.mapq);
+  fcsbq_batch d = stage_batch(b, l.batch, host, dev);
+  std::memcpy(host + l.rg, b.rg, 4 * (size_t)b.n);
   d.rg = reinterpret_cast<const int32_t*>(dev + l.rg);
-  d.cigar = reinterpret_cast<const uint32_t*>(dev + l.cigar);
-  d.cigar_off = reinterpret_cast<const int64_t*>(dev + l.coff);
-  d.n_cigar = (int64_t)nc;
-  d.bases = reinterpret_cast<const uint8_t*>(dev + l.bases);
-  d.qual = reinterpret_cast<const uint8_t*>(dev + l.qual);
-  d.base_off = reinterpret_cast<const int64_t*>(dev + l.boff);
-  d.n_bases = (int64_t)nb;
-  d.qual_absent = reinterpret_cast<const uint8_t*>(dev + l.absent);
   return d;
 }
-
-struct Release {
-  CallSession& s;
-  ~Release() { call_session_release(s); }
-};
 
 }  // namespace
 
@@ -398,13 +345,13 @@ extern "C" {
 int fcsbq_ref_create(int32_t device, const uint8_t* bases, const int64_t* ref_off, int32_t n_ref,
                      const uint64_t* known_bits, fcsbq_ref** handle) {
   const char* who = "fcsbq_ref_create";
-  if (!handle) return bq_fail(who, "null handle pointer");
+  if (!handle) return fail_invalid(who, "null handle pointer");
   *handle = nullptr;
-  if (n_ref < 0 || !ref_off || ref_off[0] != 0) return bq_fail(who, "bad ref_off or contig count");
+  if (n_ref < 0 || !ref_off || ref_off[0] != 0) return fail_invalid(who, "bad ref_off or contig count");
   for (int32_t k = 0; k < n_ref; ++k)
-    if (ref_off[k + 1] < ref_off[k]) return bq_fail(who, "ref_off is not non-decreasing at contig " + std::to_string(k));
+    if (ref_off[k + 1] < ref_off[k]) return fail_invalid(who, "ref_off is not non-decreasing at contig " + std::to_string(k));
   const int64_t total = ref_off[n_ref];
-  if (total > 0 && (!bases || !known_bits)) return bq_fail(who, "null bases or known-sites bitmap");
+  if (total > 0 && (!bases || !known_bits)) return fail_invalid(who, "null bases or known-sites bitmap");
   int rc;
   if ((rc = device_ok(device))) return rc;
   FCS_SET_DEVICE((device));
@@ -439,7 +386,7 @@ int fcsbq_ref_destroy(fcsbq_ref* handle) {
   if (!handle) return FCS_OK;
   {
     std::lock_guard<std::mutex> lk(g_ref_mu);
-    if (!live_refs().erase(handle)) return bq_fail("fcsbq_ref_destroy", "the reference handle is not a live one");
+    if (!live_refs().erase(handle)) return fail_invalid("fcsbq_ref_destroy", "the reference handle is not a live one");
   }
   std::unique_ptr<fcsbq_ref> h(handle);
   FCS_SET_DEVICE((h->device));
@@ -448,7 +395,7 @@ int fcsbq_ref_destroy(fcsbq_ref* handle) {
 }
 
 int64_t fcsbq_workspace_bytes(int32_t n_rg) {
-  if (n_rg < 0 || n_rg > FCSBQ_MAX_RG) return bq_fail("fcsbq_workspace_bytes", "bad read group count " + std::to_string(n_rg));
+  if (n_rg < 0 || n_rg > FCSBQ_MAX_RG) return fail_invalid("fcsbq_workspace_bytes", "bad read group count " + std::to_string(n_rg));
   return (int64_t)bq_ws_bytes(n_rg);
 }
 
@@ -458,10 +405,10 @@ int fcsbq_count_dev(const fcsbq_ref* handle, const fcsbq_batch* batch, int32_t n
   int rc = check_scalars(batch, n_rg, who);
   if (rc) return rc;
   if (!dev_status || (batch->n > 0 && n_rg > 0 && (!dev_ctx || !dev_cyc || !dev_workspace)))
-    return bq_fail(who, "null output or workspace");
+    return fail_invalid(who, "null output or workspace");
   const int64_t need = (int64_t)bq_ws_bytes(n_rg);
   if (batch->n > 0 && n_rg > 0 && workspace_bytes < need)
-    return bq_fail(who, "the workspace holds " + std::to_string(workspace_bytes) + " bytes, the call needs " + std::to_string(need));
+    return fail_invalid(who, "the workspace holds " + std::to_string(workspace_bytes) + " bytes, the call needs " + std::to_string(need));
   const fcsbq_ref* h = live_ref(handle, who);
   if (!h) return FCS_ERR_INVALID;
   FCS_SET_DEVICE((h->device));
@@ -477,7 +424,7 @@ int fcsbq_apply_dev(int32_t device, const fcsbq_batch* batch, int32_t n_rg, cons
   if (rc) return rc;
   if (!dev_status || (batch->n > 0 && n_rg > 0 && (!dev_base || !dev_dctx || !dev_dcyc)) ||
       (batch->n_bases > 0 && batch->n > 0 && !dev_out_qual))
-    return bq_fail(who, "null table or output");
+    return fail_invalid(who, "null table or output");
   if ((rc = device_ok(device))) return rc;
   FCS_SET_DEVICE((device));
   return launch_apply(*batch, n_rg, dev_base, dev_dctx, dev_dcyc, dev_out_qual, dev_status, static_cast<hipStream_t>(stream));
@@ -487,7 +434,7 @@ int fcsbq_count(const fcsbq_ref* handle, const fcsbq_batch* b, int32_t n_rg, int
   const char* who = "fcsbq_count";
   int rc = check_scalars(b, n_rg, who);
   if (rc) return rc;
-  if (n_rg > 0 && (!ctx || !cyc)) return bq_fail(who, "null table");
+  if (n_rg > 0 && (!ctx || !cyc)) return fail_invalid(who, "null table");
   if ((rc = check_arrays(b, n_rg, who))) return rc;
   const fcsbq_ref* h = live_ref(handle, who);
   if (!h) return FCS_ERR_INVALID;
@@ -499,43 +446,34 @@ int fcsbq_count(const fcsbq_ref* handle, const fcsbq_batch* b, int32_t n_rg, int
     const int64_t n_ops = b->cigar_off[r + 1] - b->cigar_off[r], L = b->base_off[r + 1] - b->base_off[r];
     int64_t lead, trail, covered;
     bq_clips(cigar, n_ops, lead, trail, covered);
-    if (covered != L) return bq_fail(who, "the CIGAR of record " + std::to_string(r) + " does not cover its bases");
+    if (covered != L) return fail_invalid(who, "the CIGAR of record " + std::to_string(r) + " does not cover its bases");
     const int32_t c = b->ref_id[r];
     if (c < 0 || c >= h->n_ref)
-      return bq_fail(who, "ref_id " + std::to_string(c) + " of record " + std::to_string(r) + " is outside [0, " +
-                              std::to_string(h->n_ref) + ")");
+      return fail_invalid(who, "ref_id " + std::to_string(c) + " of record " + std::to_string(r) + " is outside [0, " +
+                                   std::to_string(h->n_ref) + ")");
     if (L - lead - trail > FCSBQ_MAX_CYCLE)
-      return bq_fail(who, "record " + std::to_string(r) + " has " + std::to_string(L - lead - trail) +
-                              " kept bases, more than " + std::to_string(FCSBQ_MAX_CYCLE));
+      return fail_invalid(who, "record " + std::to_string(r) + " has " + std::to_string(L - lead - trail) +
+                                   " kept bases, more than " + std::to_string(FCSBQ_MAX_CYCLE));
     const int64_t clen = h->host_off[(size_t)c + 1] - h->host_off[(size_t)c];
-    int64_t p = b->pos[r];
-    for (int64_t k = 0; k < n_ops; ++k) {
-      const uint32_t op = cigar[k] & 15u;
-      const int64_t len = (int64_t)(cigar[k] >> 4);
-      if ((op == 0u || op == 7u || op == 8u) && len > 0 && (p < 0 || p + len > clen))
-        return bq_fail(who, "record " + std::to_string(r) + " has an aligned base beyond its contig");
-      if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) p += len;
-    }
+    int64_t ref_len;
+    bool beyond;
+    cigar_span(cigar, n_ops, b->pos[r], clen, covered, ref_len, beyond);
+    if (beyond) return fail_invalid(who, "record " + std::to_string(r) + " has an aligned base beyond its contig");
   }
   if (n == 0 || n_rg == 0) return FCS_OK;
   FCS_SET_DEVICE((h->device));
-  size_t total = 0;
-  const BqLayout l = layout_of(*b, total);
+  Arena A;
+  const BqLayout l = layout_of(*b, A);
+  const size_t in_bytes = A.total;
   const size_t nctx = 16 * (size_t)n_rg * kBqNq * kBqNctx, ncyc = 16 * (size_t)n_rg * kBqNq * kBqNcyc;
-  const size_t octx = total;
-  total += pad256(nctx);
-  const size_t ocyc = total;
-  total += pad256(ncyc);
-  const size_t ostatus = total;
-  total += 256;
-  const size_t host_bytes = total;
-  const size_t ows = total;
-  total += bq_ws_bytes(n_rg);
+  const size_t octx = A.add(nctx), ocyc = A.add(ncyc), ostatus = A.add(4);
+  const size_t host_bytes = A.total;
+  const size_t ows = A.add(bq_ws_bytes(n_rg));
   CallSession S;
-  if ((rc = call_session_acquire(h->device, host_bytes, total, S))) return rc;
-  Release release{S};
+  if ((rc = call_session_acquire(h->device, host_bytes, A.total, S))) return rc;
+  CallLease lease{S};
   const fcsbq_batch d = stage(*b, l, S.host, S.dev);
-  FCS_HIP_CHECK(hipMemcpyAsync(S.dev, S.host, l.in_bytes, hipMemcpyHostToDevice, S.s));
+  FCS_HIP_CHECK(hipMemcpyAsync(S.dev, S.host, in_bytes, hipMemcpyHostToDevice, S.s));
   FCS_HIP_CHECK(hipMemsetAsync(S.dev + octx, 0, ostatus - octx, S.s));
   if ((rc = launch_count(d, BqDevRef{h->bases, h->ref_off, h->known, h->n_ref}, n_rg, S.dev + ows,
                          reinterpret_cast<int64_t*>(S.dev + octx), reinterpret_cast<int64_t*>(S.dev + ocyc),
@@ -545,7 +483,7 @@ int fcsbq_count(const fcsbq_ref* handle, const fcsbq_batch* b, int32_t n_rg, int
   FCS_HIP_CHECK(hipStreamSynchronize(S.s));
   int32_t status;
   std::memcpy(&status, S.host + ostatus, sizeof status);
-  if (status & FCSBQ_STATUS_LONG) return bq_fail(who, "a record has more than " + std::to_string(FCSBQ_MAX_CYCLE) + " kept bases");
+  if (status & FCSBQ_STATUS_LONG) return fail_invalid(who, "a record has more than " + std::to_string(FCSBQ_MAX_CYCLE) + " kept bases");
   if (status) return fail(FCS_ERR_DEVICE, "[E::fcsbq_count] the device clamped a checked field (status " + std::to_string(status) + ")");
   const int64_t* dc = reinterpret_cast<const int64_t*>(S.host + octx);
   const int64_t* dy = reinterpret_cast<const int64_t*>(S.host + ocyc);
@@ -559,35 +497,28 @@ int fcsbq_apply(int32_t device, const fcsbq_batch* b, int32_t n_rg, const double
   const char* who = "fcsbq_apply";
   int rc = check_scalars(b, n_rg, who);
   if (rc) return rc;
-  if (n_rg > 0 && (!base || !dctx || !dcyc)) return bq_fail(who, "null table");
+  if (n_rg > 0 && (!base || !dctx || !dcyc)) return fail_invalid(who, "null table");
   if ((rc = check_arrays(b, n_rg, who))) return rc;
   const int64_t n = b->n;
-  if (n > 0 && b->base_off[n] > b->base_off[0] && !out_qual) return bq_fail(who, "null output");
+  if (n > 0 && b->base_off[n] > b->base_off[0] && !out_qual) return fail_invalid(who, "null output");
   for (int64_t r = 0; r < n; ++r)
     if (bq_applied(b->rg[r], b->qual_absent[r] != 0) && b->base_off[r + 1] - b->base_off[r] > FCSBQ_MAX_CYCLE)
-      return bq_fail(who, "record " + std::to_string(r) + " has " + std::to_string(b->base_off[r + 1] - b->base_off[r]) +
-                              " bases, more than " + std::to_string(FCSBQ_MAX_CYCLE));
+      return fail_invalid(who, "record " + std::to_string(r) + " has " + std::to_string(b->base_off[r + 1] - b->base_off[r]) +
+                                   " bases, more than " + std::to_string(FCSBQ_MAX_CYCLE));
   if (n == 0 || b->base_off[n] == b->base_off[0]) return FCS_OK;
   if ((rc = device_ok(device))) return rc;
   FCS_SET_DEVICE((device));
-  size_t total = 0;
-  const BqLayout l = layout_of(*b, total);
+  Arena A;
+  const BqLayout l = layout_of(*b, A);
   const size_t nbase = 8 * (size_t)std::max(n_rg, 1) * kBqNq;
-  const size_t obase = total;
-  total += pad256(nbase);
-  const size_t odctx = total;
-  total += pad256(nbase * kBqNctx);
-  const size_t odcyc = total;
-  total += pad256(nbase * kBqNcyc);
-  const size_t in_bytes = total;
-  const size_t nb = (size_t)b->base_off[n];
-  const size_t oout = total;
-  total += pad256(nb);
-  const size_t ostatus = total;
-  total += 256;
+  const size_t obase = A.add(nbase), odctx = A.add(nbase * kBqNctx), odcyc = A.add(nbase * kBqNcyc);
+  const size_t in_bytes = A.total;
+  const size_t nb = (size_t)b->base_off[n];  // the output is indexed by the caller's offsets
+  const size_t oout = A.add(nb), ostatus = A.add(4);
+  const size_t total = A.total;
   CallSession S;
   if ((rc = call_session_acquire(device, total, total, S))) return rc;
-  Release release{S};
+  CallLease lease{S};
   const fcsbq_batch d = stage(*b, l, S.host, S.dev);
   if (n_rg > 0) {
     std::memcpy(S.host + obase, base, 8 * (size_t)n_rg * kBqNq);

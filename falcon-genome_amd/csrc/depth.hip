@@ -39,6 +39,7 @@
 #include "dp_runs.h"
 #include "fcsdp.h"
 #include "fcship_internal.h"
+#include "rec_batch.h"
 
 namespace fcs {
 
@@ -54,8 +55,6 @@ static_assert(FCSDP_STATUS_FIELD == kDpStatusField && FCSDP_STATUS_REF == kDpSta
                   FCSDP_STATUS_OVERFLOW == kDpStatusOverflow, "fcsdp.h and dp_runs.h");
 static_assert(sizeof(fcsdp_piece) == 16 && sizeof(fcsdp_summary) == 32, "device layouts");
 
-__device__ __forceinline__ int64_t dp_clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
-
 __global__ __launch_bounds__(kDpBlock) void dp_runs_kernel(fcsdp_batch b, fcsdp_params prm, fcsdp_window w,
                                                            int32_t* __restrict__ cells, int32_t* __restrict__ status) {
   const int wave = (int)threadIdx.x / 64, lane = (int)threadIdx.x % 64;
@@ -64,17 +63,14 @@ __global__ __launch_bounds__(kDpBlock) void dp_runs_kernel(fcsdp_batch b, fcsdp_
   for (int64_t r = (int64_t)blockIdx.x * kDpWaves + wave; r < b.n; r += stride) {  // r is the wave's
     const int32_t c = b.ref_id[r];
     if (c != w.ref_id) continue;
-    const int64_t k0 = b.cigar_off[r], k1 = b.cigar_off[r + 1];
-    const int64_t c0 = dp_clamp64(k0, 0, b.n_cigar), c1 = dp_clamp64(k1, c0, b.n_cigar);
-    const int64_t o0 = b.base_off[r], o1 = b.base_off[r + 1];
-    const int64_t q0 = dp_clamp64(o0, 0, b.n_bases), q1 = dp_clamp64(o1, q0, b.n_bases);
+    int64_t c0, c1, q0, q1;
+    bool bad = !rec_fields(b, r, c0, c1, q0, q1);
     const uint32_t* cigar = b.cigar + c0;
     const int64_t n_ops = c1 - c0, L = q1 - q0;
-    bool bad = c0 != k0 || c1 != k1 || q0 != o0 || q1 != o1;
     int64_t covered = 0, ref_len = 0;
     if (!bad) {
       if (!dp_counted(b.flag[r], c, n_ops, b.mapq[r], prm.min_mapq, prm.max_mapq)) continue;
-      dp_span(cigar, n_ops, covered, ref_len);
+      cigar_span(cigar, n_ops, covered, ref_len);
       bad = covered != L;
     }
     if (bad) {  // the record adds nothing
@@ -91,7 +87,7 @@ __global__ __launch_bounds__(kDpBlock) void dp_runs_kernel(fcsdp_batch b, fcsdp_
       const int64_t i = i0 + lane;
       int32_t off = -1;
       int64_t p;
-      if (i < L && dp_site(cigar, n_ops, (int32_t)pos, i, p)) {
+      if (i < L && cigar_site(cigar, n_ops, pos, i, p)) {
         if (p < 0 || p >= clen) beyond = true;
         else if (dp_base_ok(absent ? 0 : (int)qual[i], prm.min_baseq, prm.max_baseq)) off = dp_in_window(p, w0, wlen, clen);
       }
@@ -108,8 +104,8 @@ __global__ __launch_bounds__(kDpBlock) void dp_runs_kernel(fcsdp_batch b, fcsdp_
         const uint32_t op = cigar[k] & 15u;
         const int64_t len = (int64_t)(cigar[k] >> 4);
         if (op == 2u) {
-          const int64_t lo = dp_clamp64(p, w0 > 0 ? w0 : 0, p + len);
-          const int64_t hi = dp_clamp64(p + len, lo, w0 + wlen < clen ? w0 + wlen : clen);
+          const int64_t lo = clamp64(p, w0 > 0 ? w0 : 0, p + len);
+          const int64_t hi = clamp64(p + len, lo, w0 + wlen < clen ? w0 + wlen : clen);
           if (lo < hi) {
             atomicAdd(cells + (lo - w0), 1);
             atomicAdd(cells + (hi - w0), -1);
@@ -121,27 +117,6 @@ __global__ __launch_bounds__(kDpBlock) void dp_runs_kernel(fcsdp_batch b, fcsdp_
   }
 }
 
-// The exclusive scan of one value per lane of the block (wrapping), and the block's total.
-__device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t& total, uint32_t* wave_sums) {
-  const int wave = (int)threadIdx.x / 64, lane = (int)threadIdx.x % 64;
-  uint32_t inc = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t up = __shfl_up(inc, d);
-    if (lane >= d) inc += up;
-  }
-  if (lane == 63) wave_sums[wave] = inc;
-  __syncthreads();
-  uint32_t before = 0;
-  total = 0;
-  for (int k = 0; k < kDpWaves; ++k) {
-    const uint32_t s = wave_sums[k];
-    if (k < wave) before += s;
-    total += s;
-  }
-  __syncthreads();  // wave_sums may be written again
-  return before + inc - v;
-}
-
 __global__ __launch_bounds__(kDpBlock) void dp_reduce_kernel(const int32_t* __restrict__ cells, int64_t len,
                                                              int64_t n_tiles, uint32_t* __restrict__ sums) {
   __shared__ uint32_t wave_sums[kDpWaves];
@@ -151,7 +126,7 @@ __global__ __launch_bounds__(kDpBlock) void dp_reduce_kernel(const int32_t* __re
     for (int k = 0; k < 4; ++k)
       if (base + k < len) v += (uint32_t)cells[base + k];
     uint32_t total;
-    (void)block_scan_excl(v, total, wave_sums);
+    (void)block_scan_excl<kDpWaves>(v, total, wave_sums);
     if (threadIdx.x == 0) sums[t] = total;
   }
 }
@@ -163,7 +138,7 @@ __global__ __launch_bounds__(kDpBlock) void dp_offsets_kernel(uint32_t* __restri
     const int64_t t = t0 + threadIdx.x;
     const uint32_t v = t < n_tiles ? sums[t] : 0;
     uint32_t total;
-    const uint32_t ex = block_scan_excl(v, total, wave_sums);
+    const uint32_t ex = block_scan_excl<kDpWaves>(v, total, wave_sums);
     if (t < n_tiles) sums[t] = carry + ex;
     carry += total;
   }
@@ -182,7 +157,7 @@ __global__ __launch_bounds__(kDpBlock) void dp_scan_kernel(int32_t* __restrict__
       s += v[k];
     }
     uint32_t total;
-    uint32_t run = offsets[t] + block_scan_excl(s, total, wave_sums);
+    uint32_t run = offsets[t] + block_scan_excl<kDpWaves>(s, total, wave_sums);
     for (int k = 0; k < 4; ++k) {
       run += v[k];
       if (base + k < len) {
@@ -212,8 +187,8 @@ __global__ __launch_bounds__(kDpBlock) void dp_stats_kernel(const uint32_t* __re
     if (tid < 3) quant[tid] = 1;
     __syncthreads();
     const fcsdp_piece p = pieces[pc];
-    const int64_t start = dp_clamp64(p.start, 0, len);
-    const int64_t end = dp_clamp64(p.end, start, start + kDpPieceMax < len ? start + kDpPieceMax : len);
+    const int64_t start = clamp64(p.start, 0, len);
+    const int64_t end = clamp64(p.end, start, start + kDpPieceMax < len ? start + kDpPieceMax : len);
     int32_t li = p.long_index;
     if (start != p.start || end != p.end || li < -1 || li >= n_long) {
       if (tid == 0) atomicOr(status, kDpStatusField);
@@ -233,7 +208,7 @@ __global__ __launch_bounds__(kDpBlock) void dp_stats_kernel(const uint32_t* __re
     __syncthreads();
     const uint32_t h0 = bins[2 * tid], h1 = bins[2 * tid + 1];
     uint32_t n;
-    const uint32_t before = block_scan_excl(h0 + h1, n, wave_sums);
+    const uint32_t before = block_scan_excl<kDpWaves>(h0 + h1, n, wave_sums);
     if (n > 0 && li < 0)
       for (int k = 1; k <= 3; ++k) {
         if (h0 && dp_is_quantile(before, before + h0, n, k)) quant[k - 1] = dp_reported(2 * tid);
@@ -255,8 +230,6 @@ __global__ __launch_bounds__(kDpBlock) void dp_stats_kernel(const uint32_t* __re
     __syncthreads();  // the shared cells are zeroed again
   }
 }
-
-int dp_fail(const char* who, const std::string& what) { return fail(FCS_ERR_INVALID, std::string("[E::") + who + "] " + what); }
 
 int dp_grid(int64_t items, int per_block) {
   return (int)std::clamp<int64_t>((items + per_block - 1) / per_block, 1, kDpMaxBlocks);
@@ -298,64 +271,31 @@ int launch_stats(const uint32_t* depth, const uint64_t* bitmap, int64_t len, con
 }
 
 int check_params(const fcsdp_params* p, const char* who) {
-  if (!p) return dp_fail(who, "null parameters");
+  if (!p) return fail_invalid(who, "null parameters");
   if (p->min_mapq > p->max_mapq || p->min_baseq > p->max_baseq)
-    return dp_fail(who, "a lower bound above its upper bound (MAPQ " + std::to_string(p->min_mapq) + " .. " +
-                            std::to_string(p->max_mapq) + ", base quality " + std::to_string(p->min_baseq) + " .. " +
-                            std::to_string(p->max_baseq) + ")");
+    return fail_invalid(who, "a lower bound above its upper bound (MAPQ " + std::to_string(p->min_mapq) + " .. " +
+                                 std::to_string(p->max_mapq) + ", base quality " + std::to_string(p->min_baseq) + " .. " +
+                                 std::to_string(p->max_baseq) + ")");
   return FCS_OK;
 }
 
 int check_window(const fcsdp_window* w, const char* who) {
-  if (!w) return dp_fail(who, "null window");
-  if (w->ref_id < 0) return dp_fail(who, "window ref_id " + std::to_string(w->ref_id));
+  if (!w) return fail_invalid(who, "null window");
+  if (w->ref_id < 0) return fail_invalid(who, "window ref_id " + std::to_string(w->ref_id));
   if (w->len < 0 || w->len > FCSDP_WINDOW_MAX)
-    return dp_fail(who, "a window of " + std::to_string(w->len) + " loci (at most " + std::to_string(FCSDP_WINDOW_MAX) + ")");
+    return fail_invalid(who, "a window of " + std::to_string(w->len) + " loci (at most " + std::to_string(FCSDP_WINDOW_MAX) + ")");
   if (w->start < 0 || w->contig_len < 0 || w->start + w->len > w->contig_len)
-    return dp_fail(who, "the window " + std::to_string(w->start) + " + " + std::to_string(w->len) +
-                            " lies outside its contig of " + std::to_string(w->contig_len) + " bases");
-  return FCS_OK;
-}
-
-int check_batch_scalars(const fcsdp_batch* b, const char* who) {
-  if (!b) return dp_fail(who, "null batch");
-  if (b->n < 0) return dp_fail(who, "negative record count " + std::to_string(b->n));
-  if (b->n_cigar < 0 || b->n_bases < 0) return dp_fail(who, "negative CIGAR or base size");
-  if (b->n > 0 && (!b->flag || !b->ref_id || !b->pos || !b->mapq || !b->cigar_off || !b->base_off || !b->qual_absent))
-    return dp_fail(who, "null array");
-  if ((b->n_cigar > 0 && !b->cigar) || (b->n_bases > 0 && !b->qual)) return dp_fail(who, "null CIGAR or quality bytes");
-  return FCS_OK;
-}
-
-int check_batch_arrays(const fcsdp_batch* b, const char* who) {
-  const int64_t n = b->n;
-  for (int k = 0; k < 2; ++k) {
-    const int64_t* off = k ? b->base_off : b->cigar_off;
-    const int64_t total = k ? b->n_bases : b->n_cigar;
-    const char* what = k ? "base" : "CIGAR";
-    if (n > 0 && off[0] < 0) return dp_fail(who, std::string(what) + " offsets start below zero");
-    for (int64_t r = 0; r < n; ++r)
-      if (off[r + 1] < off[r]) return dp_fail(who, std::string(what) + " offsets out of order at record " + std::to_string(r));
-    if (n > 0 && off[n] > total)
-      return dp_fail(who, std::string(what) + " offsets end at " + std::to_string(off[n]) + ", beyond the " +
-                              std::to_string(total) + " given");
-  }
+    return fail_invalid(who, "the window " + std::to_string(w->start) + " + " + std::to_string(w->len) +
+                                 " lies outside its contig of " + std::to_string(w->contig_len) + " bases");
   return FCS_OK;
 }
 
 int check_stats_scalars(int64_t len, int64_t n_pieces, int32_t n_long, const char* who) {
-  if (len < 0 || len > FCSDP_WINDOW_MAX) return dp_fail(who, "a window of " + std::to_string(len) + " loci");
-  if (n_pieces < 0 || n_pieces > FCSDP_WINDOW_MAX) return dp_fail(who, "bad piece count " + std::to_string(n_pieces));
-  if (n_long < 0 || n_long > (1 << 20)) return dp_fail(who, "bad long interval count " + std::to_string(n_long));
+  if (len < 0 || len > FCSDP_WINDOW_MAX) return fail_invalid(who, "a window of " + std::to_string(len) + " loci");
+  if (n_pieces < 0 || n_pieces > FCSDP_WINDOW_MAX) return fail_invalid(who, "bad piece count " + std::to_string(n_pieces));
+  if (n_long < 0 || n_long > (1 << 20)) return fail_invalid(who, "bad long interval count " + std::to_string(n_long));
   return FCS_OK;
 }
-
-size_t pad256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-struct Release {
-  CallSession& s;
-  ~Release() { call_session_release(s); }
-};
 
 }  // namespace
 
@@ -366,7 +306,7 @@ using namespace fcs;
 extern "C" {
 
 int64_t fcsdp_workspace_bytes(int64_t len) {
-  if (len < 0 || len > FCSDP_WINDOW_MAX) return dp_fail("fcsdp_workspace_bytes", "a window of " + std::to_string(len) + " loci");
+  if (len < 0 || len > FCSDP_WINDOW_MAX) return fail_invalid("fcsdp_workspace_bytes", "a window of " + std::to_string(len) + " loci");
   return (int64_t)dp_ws_bytes(len);
 }
 
@@ -374,8 +314,8 @@ int fcsdp_runs_dev(int32_t device, const fcsdp_batch* batch, const fcsdp_params*
                    int32_t* dev_cells, int32_t* dev_status, void* stream) {
   const char* who = "fcsdp_runs_dev";
   int rc;
-  if ((rc = check_batch_scalars(batch, who)) || (rc = check_params(params, who)) || (rc = check_window(window, who))) return rc;
-  if (!dev_status || (batch->n > 0 && window->len > 0 && !dev_cells)) return dp_fail(who, "null cells or status");
+  if ((rc = check_batch_scalars(batch, false, who)) || (rc = check_params(params, who)) || (rc = check_window(window, who))) return rc;
+  if (!dev_status || (batch->n > 0 && window->len > 0 && !dev_cells)) return fail_invalid(who, "null cells or status");
   if ((rc = device_ok(device))) return rc;
   FCS_SET_DEVICE((device));
   return launch_runs(*batch, *params, *window, dev_cells, dev_status, static_cast<hipStream_t>(stream));
@@ -384,11 +324,11 @@ int fcsdp_runs_dev(int32_t device, const fcsdp_batch* batch, const fcsdp_params*
 int fcsdp_scan_dev(int32_t device, int32_t* dev_cells, int64_t len, void* dev_workspace, int64_t workspace_bytes,
                    int32_t* dev_status, void* stream) {
   const char* who = "fcsdp_scan_dev";
-  if (len < 0 || len > FCSDP_WINDOW_MAX) return dp_fail(who, "a window of " + std::to_string(len) + " loci");
-  if (!dev_status || (len > 0 && (!dev_cells || !dev_workspace))) return dp_fail(who, "null cells, workspace or status");
+  if (len < 0 || len > FCSDP_WINDOW_MAX) return fail_invalid(who, "a window of " + std::to_string(len) + " loci");
+  if (!dev_status || (len > 0 && (!dev_cells || !dev_workspace))) return fail_invalid(who, "null cells, workspace or status");
   const int64_t need = (int64_t)dp_ws_bytes(len);
   if (len > 0 && workspace_bytes < need)
-    return dp_fail(who, "the workspace holds " + std::to_string(workspace_bytes) + " bytes, the call needs " + std::to_string(need));
+    return fail_invalid(who, "the workspace holds " + std::to_string(workspace_bytes) + " bytes, the call needs " + std::to_string(need));
   int rc;
   if ((rc = device_ok(device))) return rc;
   FCS_SET_DEVICE((device));
@@ -403,7 +343,7 @@ int fcsdp_stats_dev(int32_t device, const uint32_t* dev_depth, const uint64_t* d
   if ((rc = check_stats_scalars(len, n_pieces, n_long, who))) return rc;
   if (!dev_status || (n_pieces > 0 && (!dev_pieces || !dev_hist || !dev_summary || (len > 0 && (!dev_depth || !dev_bitmap)) ||
                                         (n_long > 0 && !dev_long_hist))))
-    return dp_fail(who, "null input, table or status");
+    return fail_invalid(who, "null input, table or status");
   if ((rc = device_ok(device))) return rc;
   FCS_SET_DEVICE((device));
   return launch_stats(dev_depth, dev_bitmap, len, dev_pieces, n_pieces, n_long, dev_hist, dev_long_hist, dev_summary,
@@ -413,9 +353,9 @@ int fcsdp_stats_dev(int32_t device, const uint32_t* dev_depth, const uint64_t* d
 int fcsdp_count(int32_t device, const fcsdp_batch* b, const fcsdp_params* prm, const fcsdp_window* w, uint32_t* depth) {
   const char* who = "fcsdp_count";
   int rc;
-  if ((rc = check_batch_scalars(b, who)) || (rc = check_params(prm, who)) || (rc = check_window(w, who))) return rc;
-  if (w->len > 0 && !depth) return dp_fail(who, "null depth array");
-  if ((rc = check_batch_arrays(b, who))) return rc;
+  if ((rc = check_batch_scalars(b, false, who)) || (rc = check_params(prm, who)) || (rc = check_window(w, who))) return rc;
+  if (w->len > 0 && !depth) return fail_invalid(who, "null depth array");
+  if ((rc = check_batch_offsets(b, who))) return rc;
   const int64_t n = b->n;
   // what the rules refuse, before any device work
   for (int64_t r = 0; r < n; ++r) {
@@ -424,61 +364,24 @@ int fcsdp_count(int32_t device, const fcsdp_batch* b, const fcsdp_params* prm, c
     const int64_t n_ops = b->cigar_off[r + 1] - b->cigar_off[r], L = b->base_off[r + 1] - b->base_off[r];
     if (!dp_counted(b->flag[r], b->ref_id[r], n_ops, b->mapq[r], prm->min_mapq, prm->max_mapq)) continue;
     int64_t covered, ref_len;
-    dp_span(cigar, n_ops, covered, ref_len);
-    if (covered != L) return dp_fail(who, "the CIGAR of record " + std::to_string(r) + " does not cover its bases");
-    int64_t p = b->pos[r];
-    for (int64_t k = 0; k < n_ops; ++k) {
-      const uint32_t op = cigar[k] & 15u;
-      const int64_t len = (int64_t)(cigar[k] >> 4);
-      if ((op == 0u || op == 7u || op == 8u) && len > 0 && (p < 0 || p + len > w->contig_len))
-        return dp_fail(who, "record " + std::to_string(r) + " has an aligned base beyond its contig");
-      if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) p += len;
-    }
+    bool beyond;
+    cigar_span(cigar, n_ops, b->pos[r], w->contig_len, covered, ref_len, beyond);
+    if (covered != L) return fail_invalid(who, "the CIGAR of record " + std::to_string(r) + " does not cover its bases");
+    if (beyond) return fail_invalid(who, "record " + std::to_string(r) + " has an aligned base beyond its contig");
   }
   if (n == 0 || w->len == 0) return FCS_OK;
   if ((rc = device_ok(device))) return rc;
   FCS_SET_DEVICE((device));
-  const size_t N = (size_t)n, c_lo = (size_t)b->cigar_off[0], nc = (size_t)b->cigar_off[n] - c_lo;
-  const size_t b_lo = (size_t)b->base_off[0], nb = (size_t)b->base_off[n] - b_lo;
-  size_t total = 0;
-  auto add = [&](size_t bytes) {
-    const size_t o = total;
-    total += pad256(bytes);
-    return o;
-  };
-  const size_t oflag = add(2 * N), oref = add(4 * N), opos = add(4 * N), omapq = add(N), oabs = add(N);
-  const size_t ocoff = add(8 * (N + 1)), oboff = add(8 * (N + 1)), ocig = add(4 * nc), oqual = add(nb);
-  const size_t in_bytes = total;
-  const size_t ocells = add(4 * ((size_t)w->len + 1)), ostatus = add(4);
-  const size_t host_bytes = total;
-  const size_t ows = add(dp_ws_bytes(w->len));
+  Arena A;
+  const BatchLayout l = layout_batch(*b, false, A);
+  const size_t in_bytes = A.total;
+  const size_t ocells = A.add(4 * ((size_t)w->len + 1)), ostatus = A.add(4);
+  const size_t host_bytes = A.total;
+  const size_t ows = A.add(dp_ws_bytes(w->len));
   CallSession S;
-  if ((rc = call_session_acquire(device, host_bytes, total, S))) return rc;
-  Release release{S};
-  std::memcpy(S.host + oflag, b->flag, 2 * N);
-  std::memcpy(S.host + oref, b->ref_id, 4 * N);
-  std::memcpy(S.host + opos, b->pos, 4 * N);
-  std::memcpy(S.host + omapq, b->mapq, N);
-  std::memcpy(S.host + oabs, b->qual_absent, N);
-  std::memcpy(S.host + ocoff, b->cigar_off, 8 * (N + 1));
-  std::memcpy(S.host + oboff, b->base_off, 8 * (N + 1));
-  if (nc) std::memcpy(S.host + ocig, b->cigar + c_lo, 4 * nc);
-  if (nb) std::memcpy(S.host + oqual, b->qual + b_lo, nb);
-  // the device view keeps the caller's offsets: its CIGAR and quality bases are shifted down by the first ones
-  fcsdp_batch d;
-  d.n = n;
-  d.flag = reinterpret_cast<const uint16_t*>(S.dev + oflag);
-  d.ref_id = reinterpret_cast<const int32_t*>(S.dev + oref);
-  d.pos = reinterpret_cast<const int32_t*>(S.dev + opos);
-  d.mapq = reinterpret_cast<const uint8_t*>(S.dev + omapq);
-  d.cigar = reinterpret_cast<const uint32_t*>(S.dev + ocig) - c_lo;
-  d.cigar_off = reinterpret_cast<const int64_t*>(S.dev + ocoff);
-  d.n_cigar = b->cigar_off[n];
-  d.bases = nullptr;
-  d.qual = reinterpret_cast<const uint8_t*>(S.dev + oqual) - b_lo;
-  d.base_off = reinterpret_cast<const int64_t*>(S.dev + oboff);
-  d.n_bases = b->base_off[n];
-  d.qual_absent = reinterpret_cast<const uint8_t*>(S.dev + oabs);
+  if ((rc = call_session_acquire(device, host_bytes, A.total, S))) return rc;
+  CallLease lease{S};
+  const fcsdp_batch d = stage_batch(*b, l, S.host, S.dev);
   int32_t* cells = reinterpret_cast<int32_t*>(S.dev + ocells);
   int32_t* status = reinterpret_cast<int32_t*>(S.dev + ostatus);
   FCS_HIP_CHECK(hipMemcpyAsync(S.dev, S.host, in_bytes, hipMemcpyHostToDevice, S.s));
@@ -489,7 +392,7 @@ int fcsdp_count(int32_t device, const fcsdp_batch* b, const fcsdp_params* prm, c
   FCS_HIP_CHECK(hipStreamSynchronize(S.s));
   int32_t st;
   std::memcpy(&st, S.host + ostatus, sizeof st);
-  if (st & FCSDP_STATUS_OVERFLOW) return dp_fail(who, "a depth beyond 2^31 - 1");
+  if (st & FCSDP_STATUS_OVERFLOW) return fail_invalid(who, "a depth beyond 2^31 - 1");
   if (st) return fail(FCS_ERR_DEVICE, "[E::fcsdp_count] the device clamped a checked field (status " + std::to_string(st) + ")");
   const uint32_t* got = reinterpret_cast<const uint32_t*>(S.host + ocells);
   for (int64_t i = 0; i < w->len; ++i) depth[i] += got[i];
@@ -502,34 +405,30 @@ int fcsdp_stats(int32_t device, const uint32_t* depth, const uint64_t* bitmap, i
   int rc;
   if ((rc = check_stats_scalars(len, n_pieces, n_long, who))) return rc;
   if (n_pieces > 0 && (!pieces || !hist || !summary || (len > 0 && (!depth || !bitmap)) || (n_long > 0 && !long_hist)))
-    return dp_fail(who, "null input or table");
+    return fail_invalid(who, "null input or table");
   for (int64_t k = 0; k < n_pieces; ++k) {
     const fcsdp_piece& p = pieces[k];
     if (p.start < 0 || p.end < p.start || p.end > len || p.end - p.start > FCSDP_PIECE_MAX)
-      return dp_fail(who, "piece " + std::to_string(k) + " [" + std::to_string(p.start) + ", " + std::to_string(p.end) +
-                              ") is outside the window of " + std::to_string(len) + " loci or longer than " +
-                              std::to_string(FCSDP_PIECE_MAX));
+      return fail_invalid(who, "piece " + std::to_string(k) + " [" + std::to_string(p.start) + ", " + std::to_string(p.end) +
+                                   ") is outside the window of " + std::to_string(len) + " loci or longer than " +
+                                   std::to_string(FCSDP_PIECE_MAX));
     if (p.long_index < -1 || p.long_index >= n_long)
-      return dp_fail(who, "long_index " + std::to_string(p.long_index) + " of piece " + std::to_string(k) + " is outside [-1, " +
-                              std::to_string(n_long) + ")");
+      return fail_invalid(who, "long_index " + std::to_string(p.long_index) + " of piece " + std::to_string(k) + " is outside [-1, " +
+                                   std::to_string(n_long) + ")");
   }
   if (n_pieces == 0) return FCS_OK;
   if ((rc = device_ok(device))) return rc;
   FCS_SET_DEVICE((device));
   const size_t words = (size_t)(len + 63) / 64, np = (size_t)n_pieces;
-  size_t total = 0;
-  auto add = [&](size_t bytes) {
-    const size_t o = total;
-    total += pad256(bytes);
-    return o;
-  };
-  const size_t odepth = add(4 * (size_t)len), obits = add(8 * words), opieces = add(sizeof(fcsdp_piece) * np);
-  const size_t in_bytes = total;
-  const size_t ohist = add(8 * (size_t)kDpBins), olong = add(8 * (size_t)kDpBins * (size_t)n_long);
-  const size_t osum = add(sizeof(fcsdp_summary) * np), ostatus = add(4);
+  Arena A;
+  const size_t odepth = A.add(4 * (size_t)len), obits = A.add(8 * words), opieces = A.add(sizeof(fcsdp_piece) * np);
+  const size_t in_bytes = A.total;
+  const size_t ohist = A.add(8 * (size_t)kDpBins), olong = A.add(8 * (size_t)kDpBins * (size_t)n_long);
+  const size_t osum = A.add(sizeof(fcsdp_summary) * np), ostatus = A.add(4);
+  const size_t total = A.total;
   CallSession S;
   if ((rc = call_session_acquire(device, total, total, S))) return rc;
-  Release release{S};
+  CallLease lease{S};
   if (len > 0) std::memcpy(S.host + odepth, depth, 4 * (size_t)len), std::memcpy(S.host + obits, bitmap, 8 * words);
   std::memcpy(S.host + opieces, pieces, sizeof(fcsdp_piece) * np);
   FCS_HIP_CHECK(hipMemcpyAsync(S.dev, S.host, in_bytes, hipMemcpyHostToDevice, S.s));

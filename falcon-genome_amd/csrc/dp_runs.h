@@ -4,16 +4,17 @@
 // at a time, so that a lane can take a base.
 //
 //   dp_counted    the record filter (ref_id, CIGAR, flags, MAPQ bounds)
-//   dp_span       the read bases the CIGAR covers and the reference span
-//   dp_site       whether read base i is aligned (M / = / X), and where
 //   dp_base_ok    the base quality bounds
 //   dp_in_window  the window offset of a counted position, or -1
 //   dp_run_first / dp_run_last   the ends of the maximal runs of counted bases
 //                 at consecutive positions among 64 neighbours
 //   dp_bin / dp_quantile         the histogram bin and the granular quantile
+// The CIGAR walks (cigar_span, cigar_site) are cigar_walk.h's.
 #pragma once
 
 #include <stdint.h>
+
+#include "cigar_walk.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -30,41 +31,6 @@ constexpr int kDpStatusField = 1, kDpStatusRef = 2, kDpStatusOverflow = 4;
 
 DP_HD bool dp_counted(uint16_t flag, int32_t ref_id, int64_t n_ops, uint8_t mapq, int32_t min_mapq, int32_t max_mapq) {
   return ref_id >= 0 && n_ops > 0 && (flag & kDpFlagFilter) == 0 && (int32_t)mapq >= min_mapq && (int32_t)mapq <= max_mapq;
-}
-
-// One pass over the record's n_ops CIGAR words (len << 4 | op): the read bases
-// of S / M / I / = / X and the reference bases of M / D / N / = / X.
-DP_HD void dp_span(const uint32_t* cigar, int64_t n_ops, int64_t& covered, int64_t& ref_len) {
-  covered = ref_len = 0;
-  for (int64_t k = 0; k < n_ops; ++k) {
-    const uint32_t op = cigar[k] & 15u;
-    const int64_t len = (int64_t)(cigar[k] >> 4);
-    if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) covered += len;
-    if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) ref_len += len;
-  }
-}
-
-// Read base i (0 <= i < covered): true, with its reference position in p, when it lies in M, = or X.
-DP_HD bool dp_site(const uint32_t* cigar, int64_t n_ops, int32_t pos, int64_t i, int64_t& p) {
-  int64_t q = 0, r = pos;
-  for (int64_t k = 0; k < n_ops; ++k) {
-    const uint32_t op = cigar[k] & 15u;
-    const int64_t len = (int64_t)(cigar[k] >> 4);
-    if (op == 0u || op == 7u || op == 8u) {
-      if (i < q + len) {
-        p = r + (i - q);
-        return true;
-      }
-      q += len, r += len;
-    } else if (op == 1u || op == 4u) {
-      if (i < q + len) break;
-      q += len;
-    } else if (op == 2u || op == 3u) {
-      r += len;
-    }
-  }
-  p = 0;
-  return false;
 }
 
 DP_HD bool dp_base_ok(int q, int32_t min_baseq, int32_t max_baseq) { return q >= min_baseq && q <= max_baseq; }

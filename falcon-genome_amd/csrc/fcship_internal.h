@@ -13,6 +13,10 @@ namespace fcs {
 // ------------------------------------------------------------ error plumbing
 void set_error(const std::string& msg);
 int fail(int code, const std::string& msg);
+// FCS_ERR_INVALID with "[E::who] what".
+inline int fail_invalid(const char* who, const std::string& what) {
+  return fail(FCS_ERR_INVALID, std::string("[E::") + who + "] " + what);
+}
 #define FCS_HIP_CHECK(expr)                                                                  \
   do {                                                                                       \
     hipError_t _e = (expr);                                                                  \
@@ -323,6 +327,11 @@ struct CallSession {
 };
 int call_session_acquire(int device, size_t host_bytes, size_t dev_bytes, CallSession& c);
 void call_session_release(CallSession& c);
+// Gives an acquired session back on every path out of the call.
+struct CallLease {
+  CallSession& s;
+  ~CallLease() { call_session_release(s); }
+};
 // FCS_OK when `device` is a visible ordinal (FCS_ERR_DEVICE without any device).
 int device_ok(int device);
 

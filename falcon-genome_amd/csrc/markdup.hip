@@ -46,6 +46,7 @@
 #include "fcsdup.h"
 #include "fcship_internal.h"
 #include "md_keys.h"
+#include "rec_batch.h"
 
 namespace fcs {
 
@@ -63,24 +64,19 @@ struct MdWs {
 
 MdWs md_ws(int64_t n_records) {
   const size_t n = (size_t)std::max<int64_t>(n_records, 1);
-  size_t total = 0;
-  auto add = [&](size_t bytes) {
-    const size_t o = total;
-    total += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
+  Arena A;
   MdWs w;
-  w.endk = add(8 * n), w.score = add(4 * n), w.ex = add(n), w.wfrag = add(8 * n), w.wpair = add(8 * n);
-  w.fkey = add(8 * n), w.fval = add(4 * n), w.phi = add(8 * n), w.plo = add(8 * n), w.pval = add(4 * n);
-  w.k64a = add(8 * n), w.k64b = add(8 * n), w.v32a = add(4 * n), w.v32b = add(4 * n);
-  w.head = add(4 * n), w.seg = add(4 * n), w.best = add(8 * n);
+  w.endk = A.add(8 * n), w.score = A.add(4 * n), w.ex = A.add(n), w.wfrag = A.add(8 * n), w.wpair = A.add(8 * n);
+  w.fkey = A.add(8 * n), w.fval = A.add(4 * n), w.phi = A.add(8 * n), w.plo = A.add(8 * n), w.pval = A.add(4 * n);
+  w.k64a = A.add(8 * n), w.k64b = A.add(8 * n), w.v32a = A.add(4 * n), w.v32b = A.add(4 * n);
+  w.head = A.add(4 * n), w.seg = A.add(4 * n), w.best = A.add(8 * n);
   // rocPRIM's scratch for a sort of n (64-bit key, 32-bit value) pairs with
   // separate outputs: a second key and value array, histograms and look-back
   // states.  Reserved by a formula so that the size is known without a device;
   // every launch checks what rocPRIM asks for against it.
   w.tmp_bytes = 24 * n + ((size_t)4 << 20);
-  w.tmp = add(w.tmp_bytes);
-  w.total = total;
+  w.tmp = A.add(w.tmp_bytes);
+  w.total = A.total;
   return w;
 }
 
@@ -91,8 +87,6 @@ __device__ __forceinline__ uint32_t row_sum(uint32_t v) {
   v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kDppRowRor1, 0xF, 0xF, false);
   return v;
 }
-
-__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 __global__ __launch_bounds__(kMdBlock) void md_ends_kernel(MdDevBatch b, int32_t n_ref, int32_t n_lib,
                                                            uint64_t* __restrict__ endk, uint32_t* __restrict__ score,
@@ -273,8 +267,6 @@ __global__ __launch_bounds__(kMdBlock) void md_resolve_mark_kernel(const uint64_
 
 int grid_for(int64_t items) { return (int)std::min<int64_t>((items + kMdBlock - 1) / kMdBlock, kMdMaxBlocks); }
 
-int md_fail(const char* who, const std::string& what) { return fail(FCS_ERR_INVALID, std::string("[E::") + who + "] " + what); }
-
 #define MD_ROCPRIM(expr)                                                                                     \
   do {                                                                                                       \
     hipError_t _e = (expr);                                                                                  \
@@ -355,20 +347,20 @@ int launch_markdup(const MdDevBatch& b, int32_t n_ref, int32_t n_lib, char* ws, 
 
 // The scalar fields of a batch, checked alike by both entry points.
 int check_scalars(const fcsdup_batch* b, const char* who) {
-  if (!b) return md_fail(who, "null batch");
-  if (b->n < 0) return md_fail(who, "negative record count " + std::to_string(b->n));
+  if (!b) return fail_invalid(who, "null batch");
+  if (b->n < 0) return fail_invalid(who, "negative record count " + std::to_string(b->n));
   if (b->n > kMdMaxRecords)
-    return md_fail(who, std::to_string(b->n) + " records: more than the " + std::to_string(kMdMaxRecords) + " a batch holds");
-  if (b->n_cigar < 0 || b->n_qual < 0) return md_fail(who, "negative CIGAR or quality size");
+    return fail_invalid(who, std::to_string(b->n) + " records: more than the " + std::to_string(kMdMaxRecords) + " a batch holds");
+  if (b->n_cigar < 0 || b->n_qual < 0) return fail_invalid(who, "negative CIGAR or quality size");
   if (b->n_ref < 0 || b->n_ref > kMdMaxRefs)
-    return md_fail(who, std::to_string(b->n_ref) + " reference sequences do not fit the key's " +
-                            std::to_string(kMdRefBits) + " bits (at most " + std::to_string(kMdMaxRefs) + ")");
+    return fail_invalid(who, std::to_string(b->n_ref) + " reference sequences do not fit the key's " +
+                                 std::to_string(kMdRefBits) + " bits (at most " + std::to_string(kMdMaxRefs) + ")");
   if (b->n_lib < 0 || b->n_lib > kMdMaxLibs)
-    return md_fail(who, std::to_string(b->n_lib) + " libraries do not fit the key's " + std::to_string(kMdLibBits) +
-                            " bits (at most " + std::to_string(kMdMaxLibs) + ")");
+    return fail_invalid(who, std::to_string(b->n_lib) + " libraries do not fit the key's " + std::to_string(kMdLibBits) +
+                                 " bits (at most " + std::to_string(kMdMaxLibs) + ")");
   if (b->n > 0 && (!b->flag || !b->ref_id || !b->pos || !b->mate || !b->lib || !b->cigar_off || !b->qual_off))
-    return md_fail(who, "null array");
-  if ((b->n_cigar > 0 && !b->cigar) || (b->n_qual > 0 && !b->qual)) return md_fail(who, "null CIGAR or quality bytes");
+    return fail_invalid(who, "null array");
+  if ((b->n_cigar > 0 && !b->cigar) || (b->n_qual > 0 && !b->qual)) return fail_invalid(who, "null CIGAR or quality bytes");
   return FCS_OK;
 }
 
@@ -386,7 +378,7 @@ using namespace fcs;
 extern "C" {
 
 int64_t fcsdup_workspace_bytes(int64_t n) {
-  if (n < 0 || n > kMdMaxRecords) return md_fail("fcsdup_workspace_bytes", "bad record count " + std::to_string(n));
+  if (n < 0 || n > kMdMaxRecords) return fail_invalid("fcsdup_workspace_bytes", "bad record count " + std::to_string(n));
   return (int64_t)md_ws(n).total;
 }
 
@@ -396,11 +388,11 @@ int fcsdup_mark_dev(int32_t device, const fcsdup_batch* batch, void* dev_workspa
   int rc = check_scalars(batch, "fcsdup_mark_dev");
   if (rc) return rc;
   if (!dev_stats || !dev_status || (batch->n > 0 && (!dev_dup || !dev_workspace)))
-    return md_fail("fcsdup_mark_dev", "null output or workspace");
+    return fail_invalid("fcsdup_mark_dev", "null output or workspace");
   const int64_t need = (int64_t)md_ws(batch->n).total;
   if (batch->n > 0 && workspace_bytes < need)
-    return md_fail("fcsdup_mark_dev", "the workspace holds " + std::to_string(workspace_bytes) + " bytes, the call needs " +
-                                          std::to_string(need));
+    return fail_invalid("fcsdup_mark_dev", "the workspace holds " + std::to_string(workspace_bytes) + " bytes, the call needs " +
+                                               std::to_string(need));
   if ((rc = device_ok(device))) return rc;
   FCS_SET_DEVICE((device));
   return launch_markdup(dev_batch(batch), batch->n_ref, batch->n_lib, static_cast<char*>(dev_workspace), dev_dup,
@@ -411,36 +403,23 @@ int fcsdup_mark(int32_t device, const fcsdup_batch* b, uint8_t* dup, fcsdup_stat
   const char* who = "fcsdup_mark";
   int rc = check_scalars(b, who);
   if (rc) return rc;
-  if (!stats || (b->n > 0 && !dup)) return md_fail(who, "null output");
+  if (!stats || (b->n > 0 && !dup)) return fail_invalid(who, "null output");
   const int64_t n = b->n;
   // every offset and index, before any device work
-  for (int k = 0; k < 2; ++k) {
-    const int64_t* off = k ? b->qual_off : b->cigar_off;
-    const int64_t total = k ? b->n_qual : b->n_cigar;
-    const char* what = k ? "quality" : "CIGAR";
-    if (n > 0 && off[0] < 0) return md_fail(who, std::string(what) + " offsets start below zero");
-    for (int64_t r = 0; r < n; ++r) {
-      if (off[r + 1] < off[r])
-        return md_fail(who, std::string(what) + " offsets out of order at record " + std::to_string(r));
-      if (k && off[r + 1] - off[r] > kMdMaxQual)
-        return md_fail(who, "record " + std::to_string(r) + " has " + std::to_string(off[r + 1] - off[r]) +
-                                " quality bytes, more than " + std::to_string(kMdMaxQual));
-    }
-    if (n > 0 && off[n] > total)
-      return md_fail(who, std::string(what) + " offsets end at " + std::to_string(off[n]) + ", beyond the " +
-                              std::to_string(total) + " given");
-  }
+  if ((rc = check_offsets(who, "CIGAR", b->cigar_off, n, b->n_cigar)) ||
+      (rc = check_offsets(who, "quality", b->qual_off, n, b->n_qual, kMdMaxQual)))
+    return rc;
   for (int64_t r = 0; r < n; ++r) {
     const int32_t m = b->mate[r];
     if (m < -1 || m >= n || m == r || (m >= 0 && b->mate[m] != r))
-      return md_fail(who, "mate " + std::to_string(m) + " of record " + std::to_string(r) +
-                              " is out of range or not its mate in turn");
+      return fail_invalid(who, "mate " + std::to_string(m) + " of record " + std::to_string(r) +
+                                   " is out of range or not its mate in turn");
     if (b->ref_id[r] < -1 || b->ref_id[r] >= b->n_ref)
-      return md_fail(who, "ref_id " + std::to_string(b->ref_id[r]) + " of record " + std::to_string(r) + " is outside [-1, " +
-                              std::to_string(b->n_ref) + ")");
+      return fail_invalid(who, "ref_id " + std::to_string(b->ref_id[r]) + " of record " + std::to_string(r) + " is outside [-1, " +
+                                   std::to_string(b->n_ref) + ")");
     if (b->lib[r] < 0 || b->lib[r] >= b->n_lib)
-      return md_fail(who, "library " + std::to_string(b->lib[r]) + " of record " + std::to_string(r) + " is outside [0, " +
-                              std::to_string(b->n_lib) + ")");
+      return fail_invalid(who, "library " + std::to_string(b->lib[r]) + " of record " + std::to_string(r) + " is outside [0, " +
+                                   std::to_string(b->n_lib) + ")");
   }
   if (n == 0) {
     std::memset(stats, 0, sizeof *stats);
@@ -448,26 +427,19 @@ int fcsdup_mark(int32_t device, const fcsdup_batch* b, uint8_t* dup, fcsdup_stat
   }
   if ((rc = device_ok(device))) return rc;
   FCS_SET_DEVICE((device));
-  const size_t N = (size_t)n, nc = (size_t)b->cigar_off[n], nq = (size_t)b->qual_off[n];
-  size_t total = 0;
-  auto add = [&](size_t bytes) {
-    const size_t o = total;
-    total += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
+  const size_t N = (size_t)n, c_lo = (size_t)b->cigar_off[0], nc = (size_t)b->cigar_off[n] - c_lo;
+  const size_t q_lo = (size_t)b->qual_off[0], nq = (size_t)b->qual_off[n] - q_lo;
+  Arena A;
   // one H2D copy of the inputs, one D2H copy of dup | stats | status
-  const size_t oflag = add(2 * N), oref = add(4 * N), opos = add(4 * N), omate = add(4 * N), olib = add(4 * N);
-  const size_t ocoff = add(8 * (N + 1)), oqoff = add(8 * (N + 1)), ocig = add(4 * nc), oqual = add(nq);
-  const size_t in_bytes = total;
-  const size_t odup = add(N), ostats = add(sizeof(fcsdup_stats)), ostatus = add(sizeof(int32_t));
-  const size_t host_bytes = total;
-  const size_t ows = add(md_ws(n).total);
+  const size_t oflag = A.add(2 * N), oref = A.add(4 * N), opos = A.add(4 * N), omate = A.add(4 * N), olib = A.add(4 * N);
+  const size_t ocoff = A.add(8 * (N + 1)), oqoff = A.add(8 * (N + 1)), ocig = A.add(4 * nc), oqual = A.add(nq);
+  const size_t in_bytes = A.total;
+  const size_t odup = A.add(N), ostats = A.add(sizeof(fcsdup_stats)), ostatus = A.add(sizeof(int32_t));
+  const size_t host_bytes = A.total;
+  const size_t ows = A.add(md_ws(n).total);
   CallSession S;
-  if ((rc = call_session_acquire(device, host_bytes, total, S))) return rc;
-  struct Release {
-    CallSession& s;
-    ~Release() { call_session_release(s); }
-  } release{S};
+  if ((rc = call_session_acquire(device, host_bytes, A.total, S))) return rc;
+  CallLease lease{S};
   std::memcpy(S.host + oflag, b->flag, 2 * N);
   std::memcpy(S.host + oref, b->ref_id, 4 * N);
   std::memcpy(S.host + opos, b->pos, 4 * N);
@@ -475,9 +447,10 @@ int fcsdup_mark(int32_t device, const fcsdup_batch* b, uint8_t* dup, fcsdup_stat
   std::memcpy(S.host + olib, b->lib, 4 * N);
   std::memcpy(S.host + ocoff, b->cigar_off, 8 * (N + 1));
   std::memcpy(S.host + oqoff, b->qual_off, 8 * (N + 1));
-  if (nc) std::memcpy(S.host + ocig, b->cigar, 4 * nc);
-  if (nq) std::memcpy(S.host + oqual, b->qual, nq);
+  if (nc) std::memcpy(S.host + ocig, b->cigar + c_lo, 4 * nc);
+  if (nq) std::memcpy(S.host + oqual, b->qual + q_lo, nq);
   FCS_HIP_CHECK(hipMemcpyAsync(S.dev, S.host, in_bytes, hipMemcpyHostToDevice, S.s));
+  // the device view keeps the caller's offsets: its CIGAR and quality bases are shifted down by the first ones
   MdDevBatch d;
   d.n = n;
   d.flag = reinterpret_cast<const uint16_t*>(S.dev + oflag);
@@ -485,12 +458,12 @@ int fcsdup_mark(int32_t device, const fcsdup_batch* b, uint8_t* dup, fcsdup_stat
   d.pos = reinterpret_cast<const int32_t*>(S.dev + opos);
   d.mate = reinterpret_cast<const int32_t*>(S.dev + omate);
   d.lib = reinterpret_cast<const int32_t*>(S.dev + olib);
-  d.cigar = reinterpret_cast<const uint32_t*>(S.dev + ocig);
+  d.cigar = reinterpret_cast<const uint32_t*>(S.dev + ocig) - c_lo;
   d.cigar_off = reinterpret_cast<const int64_t*>(S.dev + ocoff);
-  d.n_cigar = (int64_t)nc;
-  d.qual = reinterpret_cast<const uint8_t*>(S.dev + oqual);
+  d.n_cigar = b->cigar_off[n];
+  d.qual = reinterpret_cast<const uint8_t*>(S.dev + oqual) - q_lo;
   d.qual_off = reinterpret_cast<const int64_t*>(S.dev + oqoff);
-  d.n_qual = (int64_t)nq;
+  d.n_qual = b->qual_off[n];
   if ((rc = launch_markdup(d, b->n_ref, b->n_lib, S.dev + ows, reinterpret_cast<uint8_t*>(S.dev + odup),
                            reinterpret_cast<unsigned long long*>(S.dev + ostats),
                            reinterpret_cast<int32_t*>(S.dev + ostatus), S.s)))
@@ -500,8 +473,8 @@ int fcsdup_mark(int32_t device, const fcsdup_batch* b, uint8_t* dup, fcsdup_stat
   int32_t status;
   std::memcpy(&status, S.host + ostatus, sizeof status);
   if (status & FCSDUP_STATUS_POS)
-    return md_fail(who, "an unclipped 5' position does not fit the key's " + std::to_string(kMdPosBits) +
-                            " bits (|u5| < " + std::to_string(kMdPosBias) + ")");
+    return fail_invalid(who, "an unclipped 5' position does not fit the key's " + std::to_string(kMdPosBits) +
+                                 " bits (|u5| < " + std::to_string(kMdPosBias) + ")");
   if (status) return fail(FCS_ERR_DEVICE, "[E::fcsdup_mark] the device clamped a checked field (status " + std::to_string(status) + ")");
   std::memcpy(dup, S.host + odup, N);
   std::memcpy(stats, S.host + ostats, sizeof *stats);

@@ -44,6 +44,7 @@
 
 #include "fcship_internal.h"
 #include "fcsug.h"
+#include "rec_batch.h"
 #include "ug_pile.h"
 
 namespace fcs {
@@ -63,16 +64,7 @@ static_assert(FCSUG_STATUS_FIELD == kUgStatusField && FCSUG_STATUS_REF == kUgSta
                   FCSUG_STATUS_ORDER == kUgStatusOrder && FCSUG_STATUS_SITES == kUgStatusSites, "fcsug.h and ug_pile.h");
 static_assert(sizeof(fcsug_site) == 80 && sizeof(fcsug_window) == 32, "device layouts");
 
-__device__ __forceinline__ int64_t ug_clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
 __device__ __forceinline__ int64_t ug_max64(int64_t a, int64_t b) { return a > b ? a : b; }
-
-// The clamped CIGAR and base ranges of record r; false when a field was clamped.
-__device__ __forceinline__ bool ug_fields(const fcsug_batch& b, int64_t r, int64_t& c0, int64_t& c1, int64_t& q0, int64_t& q1) {
-  const int64_t k0 = b.cigar_off[r], k1 = b.cigar_off[r + 1], o0 = b.base_off[r], o1 = b.base_off[r + 1];
-  c0 = ug_clamp64(k0, 0, b.n_cigar), c1 = ug_clamp64(k1, c0, b.n_cigar);
-  q0 = ug_clamp64(o0, 0, b.n_bases), q1 = ug_clamp64(o1, q0, b.n_bases);
-  return c0 == k0 && c1 == k1 && q0 == o0 && q1 == o1;
-}
 
 // The inclusive running maximum of one value per lane of the block, and the block's maximum.
 __device__ __forceinline__ int64_t block_max_incl(int64_t v, int64_t& total, int64_t* wave_max) {
@@ -94,27 +86,6 @@ __device__ __forceinline__ int64_t block_max_incl(int64_t v, int64_t& total, int
   return inc;
 }
 
-// The exclusive scan of one count per lane of the block, and the block's total.
-__device__ __forceinline__ uint32_t block_sum_excl(uint32_t v, uint32_t& total, uint32_t* wave_sums) {
-  const int wave = (int)threadIdx.x / 64, lane = (int)threadIdx.x % 64;
-  uint32_t inc = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t up = __shfl_up(inc, d);
-    if (lane >= d) inc += up;
-  }
-  if (lane == 63) wave_sums[wave] = inc;
-  __syncthreads();
-  uint32_t before = 0;
-  total = 0;
-  for (int k = 0; k < kUgWaves; ++k) {
-    const uint32_t s = wave_sums[k];
-    if (k < wave) before += s;
-    total += s;
-  }
-  __syncthreads();  // wave_sums may be written again
-  return before + inc - v;
-}
-
 __global__ __launch_bounds__(kUgBlock) void ug_span_kernel(fcsug_batch b, fcsug_window w, int64_t n_rtiles,
                                                            int64_t* __restrict__ end, int64_t* __restrict__ key,
                                                            int64_t* __restrict__ tile_end, int64_t* __restrict__ tile_key,
@@ -127,12 +98,12 @@ __global__ __launch_bounds__(kUgBlock) void ug_span_kernel(fcsug_batch b, fcsug_
       const int64_t pos = b.pos[r];
       kp = pos;
       int64_t c0, c1, q0, q1;
-      bool bad = !ug_fields(b, r, c0, c1, q0, q1);
+      bool bad = !rec_fields(b, r, c0, c1, q0, q1);
       bool counted = false, beyond = false;
       int64_t ref_len = 0;
       if (!bad && ug_counted(b.flag[r], b.ref_id[r], c1 - c0, b.mapq[r])) {
         int64_t covered;
-        ug_span(b.cigar + c0, c1 - c0, pos, w.contig_len, covered, ref_len, beyond);
+        cigar_span(b.cigar + c0, c1 - c0, pos, w.contig_len, covered, ref_len, beyond);
         bad = covered != q1 - q0;
         counted = !bad;
       }
@@ -227,7 +198,7 @@ __device__ __forceinline__ void ug_walk(const fcsug_batch& b, int32_t min_baseq,
     const int64_t pos = b.pos[r];
     if (pos >= e) continue;
     int64_t c0, c1, q0, q1;
-    (void)ug_fields(b, r, c0, c1, q0, q1);
+    (void)rec_fields(b, r, c0, c1, q0, q1);
     const uint32_t* cigar = b.cigar + c0;
     const int64_t n_ops = c1 - c0, L = q1 - q0;
     const int mapq = b.mapq[r];
@@ -237,7 +208,7 @@ __device__ __forceinline__ void ug_walk(const fcsug_batch& b, int32_t min_baseq,
     for (int64_t i0 = 0; i0 < L; i0 += 64) {
       const int64_t i = i0 + lane;
       int64_t p;
-      if (i < L && ug_locus(cigar, n_ops, pos, i, p) && p >= s && p < e) {
+      if (i < L && cigar_site(cigar, n_ops, pos, i, p) && p >= s && p < e) {
         const int x = ug_code(bases[i]);
         const int qe = ug_qe(absent ? 0 : (int)qual[i], mapq);
         if (x < 4 && qe >= min_baseq) base((int)(p - s), x, qe, mapq);
@@ -249,7 +220,7 @@ __device__ __forceinline__ void ug_walk(const fcsug_batch& b, int32_t min_baseq,
       const uint32_t op = cigar[k] & 15u;
       const int64_t len = (int64_t)(cigar[k] >> 4);
       if (op == 2u) {
-        const int64_t d0 = ug_clamp64(p, s, e), d1 = ug_clamp64(p + len, d0, e);
+        const int64_t d0 = clamp64(p, s, e), d1 = clamp64(p + len, d0, e);
         for (int64_t j = d0 + lane; j < d1; j += 64) del((int)(j - s));
       }
       if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) p += len;
@@ -281,7 +252,7 @@ __global__ __launch_bounds__(kUgBlock) void ug_count_kernel(fcsug_batch b, fcsug
               [](int) {});
     __syncthreads();
     uint32_t total;
-    (void)block_sum_excl(tid < kUgTile / 32 ? (uint32_t)__popc(marks[tid]) : 0u, total, wave_sums);
+    (void)block_scan_excl<kUgWaves>(tid < kUgTile / 32 ? (uint32_t)__popc(marks[tid]) : 0u, total, wave_sums);
     if (tid == 0) counts[t] = total;
   }
 }
@@ -295,7 +266,7 @@ __global__ __launch_bounds__(kUgBlock) void ug_slots_kernel(uint32_t* __restrict
     const int64_t t = t0 + (int64_t)threadIdx.x;
     const uint32_t v = t < n_tiles ? counts[t] : 0;
     uint32_t total;
-    const uint32_t ex = block_sum_excl(v, total, wave_sums);
+    const uint32_t ex = block_scan_excl<kUgWaves>(v, total, wave_sums);
     if (t < n_tiles) counts[t] = carry + ex;
     carry += total;
   }
@@ -342,7 +313,7 @@ __global__ __launch_bounds__(kUgBlock) void ug_tile_kernel(fcsug_batch b, fcsug_
     for (int x = 0; x < 4; ++x) n[x] = cnt[x][tid], q[x] = qsum[x][tid];
     const bool site = ug_is_site(rc, n);
     uint32_t total;
-    const int64_t at = (int64_t)slots[t] + block_sum_excl(site ? 1u : 0u, total, wave_sums);
+    const int64_t at = (int64_t)slots[t] + block_scan_excl<kUgWaves>(site ? 1u : 0u, total, wave_sums);
     if (site && at < max_sites) {
       int64_t A[4], B[4], C[4];
       for (int x = 0; x < 4; ++x) A[x] = (int64_t)sumA[x][tid], B[x] = (int64_t)sumB[x][tid], C[x] = (int64_t)sumC[x][tid];
@@ -358,11 +329,7 @@ __global__ __launch_bounds__(kUgBlock) void ug_tile_kernel(fcsug_batch b, fcsug_
   }
 }
 
-int ug_fail(const char* who, const std::string& what) { return fail(FCS_ERR_INVALID, std::string("[E::") + who + "] " + what); }
-
 int ug_grid(int64_t items) { return (int)std::clamp<int64_t>(items, 1, kUgMaxBlocks); }
-
-size_t pad256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int64_t ug_rtiles(int64_t n) { return (n + kUgBlock - 1) / kUgBlock; }
 int64_t ug_tiles(int64_t len) { return (len + kUgTile - 1) / kUgTile; }
@@ -374,16 +341,11 @@ struct UgWorkspace {
 
 UgWorkspace ug_workspace(int64_t n, int64_t len) {
   UgWorkspace ws{};
-  size_t total = 0;
-  auto add = [&](size_t bytes) {
-    const size_t o = total;
-    total += pad256(bytes);
-    return o;
-  };
-  ws.end = add(8 * (size_t)n), ws.max_end = add(8 * (size_t)n), ws.key = add(8 * (size_t)n);
-  ws.tile_end = add(8 * (size_t)ug_rtiles(n)), ws.tile_key = add(8 * (size_t)ug_rtiles(n));
-  ws.counts = add(4 * (size_t)ug_tiles(len));
-  ws.bytes = std::max<size_t>(total, 256);
+  Arena A;
+  ws.end = A.add(8 * (size_t)n), ws.max_end = A.add(8 * (size_t)n), ws.key = A.add(8 * (size_t)n);
+  ws.tile_end = A.add(8 * (size_t)ug_rtiles(n)), ws.tile_key = A.add(8 * (size_t)ug_rtiles(n));
+  ws.counts = A.add(4 * (size_t)ug_tiles(len));
+  ws.bytes = std::max<size_t>(A.total, 256);
   return ws;
 }
 
@@ -421,47 +383,15 @@ int launch_sites(const fcsug_batch& b, const fcsug_params& prm, const fcsug_wind
 }
 
 int check_window(const fcsug_window* w, const char* who) {
-  if (!w) return ug_fail(who, "null window");
-  if (w->ref_id < 0) return ug_fail(who, "window ref_id " + std::to_string(w->ref_id));
+  if (!w) return fail_invalid(who, "null window");
+  if (w->ref_id < 0) return fail_invalid(who, "window ref_id " + std::to_string(w->ref_id));
   if (w->len < 0 || w->len > FCSUG_WINDOW_MAX)
-    return ug_fail(who, "a window of " + std::to_string(w->len) + " loci (at most " + std::to_string(FCSUG_WINDOW_MAX) + ")");
+    return fail_invalid(who, "a window of " + std::to_string(w->len) + " loci (at most " + std::to_string(FCSUG_WINDOW_MAX) + ")");
   if (w->start < 0 || w->contig_len < 0 || w->start > w->contig_len - w->len)
-    return ug_fail(who, "the window " + std::to_string(w->start) + " + " + std::to_string(w->len) +
-                            " lies outside its contig of " + std::to_string(w->contig_len) + " bases");
+    return fail_invalid(who, "the window " + std::to_string(w->start) + " + " + std::to_string(w->len) +
+                                 " lies outside its contig of " + std::to_string(w->contig_len) + " bases");
   return FCS_OK;
 }
-
-int check_batch_scalars(const fcsug_batch* b, const char* who) {
-  if (!b) return ug_fail(who, "null batch");
-  if (b->n < 0) return ug_fail(who, "negative record count " + std::to_string(b->n));
-  if (b->n_cigar < 0 || b->n_bases < 0) return ug_fail(who, "negative CIGAR or base size");
-  if (b->n > 0 && (!b->flag || !b->ref_id || !b->pos || !b->mapq || !b->cigar_off || !b->base_off || !b->qual_absent))
-    return ug_fail(who, "null array");
-  if ((b->n_cigar > 0 && !b->cigar) || (b->n_bases > 0 && (!b->qual || !b->bases)))
-    return ug_fail(who, "null CIGAR, base or quality bytes");
-  return FCS_OK;
-}
-
-int check_batch_arrays(const fcsug_batch* b, const char* who) {
-  const int64_t n = b->n;
-  for (int k = 0; k < 2; ++k) {
-    const int64_t* off = k ? b->base_off : b->cigar_off;
-    const int64_t total = k ? b->n_bases : b->n_cigar;
-    const char* what = k ? "base" : "CIGAR";
-    if (n > 0 && off[0] < 0) return ug_fail(who, std::string(what) + " offsets start below zero");
-    for (int64_t r = 0; r < n; ++r)
-      if (off[r + 1] < off[r]) return ug_fail(who, std::string(what) + " offsets out of order at record " + std::to_string(r));
-    if (n > 0 && off[n] > total)
-      return ug_fail(who, std::string(what) + " offsets end at " + std::to_string(off[n]) + ", beyond the " +
-                              std::to_string(total) + " given");
-  }
-  return FCS_OK;
-}
-
-struct Release {
-  CallSession& s;
-  ~Release() { call_session_release(s); }
-};
 
 }  // namespace
 
@@ -473,8 +403,8 @@ extern "C" {
 
 int fcsug_table(double pcr_error, int64_t* table) {
   const char* who = "fcsug_table";
-  if (!table) return ug_fail(who, "null table");
-  if (!(pcr_error > 0.0 && pcr_error < 1.0)) return ug_fail(who, "pcr_error " + std::to_string(pcr_error) + " is outside (0, 1)");
+  if (!table) return fail_invalid(who, "null table");
+  if (!(pcr_error > 0.0 && pcr_error < 1.0)) return fail_invalid(who, "pcr_error " + std::to_string(pcr_error) + " is outside (0, 1)");
   const double eps = pcr_error;
   for (int q = 0; q < FCSUG_TABLE_ROWS; ++q) {
     const double e = std::pow(10.0, -q / 10.0);
@@ -488,7 +418,7 @@ int fcsug_table(double pcr_error, int64_t* table) {
 
 int64_t fcsug_workspace_bytes(int64_t n_records, int64_t len) {
   if (n_records < 0 || len < 0 || len > FCSUG_WINDOW_MAX)
-    return ug_fail("fcsug_workspace_bytes", std::to_string(n_records) + " records and a window of " + std::to_string(len) + " loci");
+    return fail_invalid("fcsug_workspace_bytes", std::to_string(n_records) + " records and a window of " + std::to_string(len) + " loci");
   return (int64_t)ug_workspace(n_records, len).bytes;
 }
 
@@ -497,16 +427,16 @@ int fcsug_sites_dev(int32_t device, const fcsug_batch* batch, const fcsug_params
                     int64_t* dev_n_sites, void* dev_workspace, int64_t workspace_bytes, int32_t* dev_status, void* stream) {
   const char* who = "fcsug_sites_dev";
   int rc;
-  if ((rc = check_batch_scalars(batch, who))) return rc;
-  if (!params) return ug_fail(who, "null parameters");
+  if ((rc = check_batch_scalars(batch, true, who))) return rc;
+  if (!params) return fail_invalid(who, "null parameters");
   if ((rc = check_window(window, who))) return rc;
-  if (max_sites < 0) return ug_fail(who, "max_sites " + std::to_string(max_sites));
+  if (max_sites < 0) return fail_invalid(who, "max_sites " + std::to_string(max_sites));
   const bool work = batch->n > 0 && window->len > 0;
   if (!dev_status || !dev_n_sites || (work && (!dev_ref || !dev_table || !dev_workspace || (max_sites > 0 && !dev_sites))))
-    return ug_fail(who, "null reference, table, sites, count, workspace or status");
+    return fail_invalid(who, "null reference, table, sites, count, workspace or status");
   const int64_t need = (int64_t)ug_workspace(batch->n, window->len).bytes;
   if (work && workspace_bytes < need)
-    return ug_fail(who, "the workspace holds " + std::to_string(workspace_bytes) + " bytes, the call needs " + std::to_string(need));
+    return fail_invalid(who, "the workspace holds " + std::to_string(workspace_bytes) + " bytes, the call needs " + std::to_string(need));
   if ((rc = device_ok(device))) return rc;
   FCS_SET_DEVICE((device));
   return launch_sites(*batch, *params, *window, dev_ref, dev_table, dev_sites, max_sites, dev_n_sites,
@@ -517,28 +447,28 @@ int fcsug_sites(int32_t device, const fcsug_batch* b, const fcsug_params* prm, c
                 const int64_t* table, fcsug_site* sites, int64_t max_sites, int64_t* n_sites) {
   const char* who = "fcsug_sites";
   int rc;
-  if ((rc = check_batch_scalars(b, who))) return rc;
-  if (!prm) return ug_fail(who, "null parameters");
+  if ((rc = check_batch_scalars(b, true, who))) return rc;
+  if (!prm) return fail_invalid(who, "null parameters");
   if ((rc = check_window(w, who))) return rc;
-  if (max_sites < 0) return ug_fail(who, "max_sites " + std::to_string(max_sites));
-  if (!n_sites || !table || (w->len > 0 && !ref) || (max_sites > 0 && !sites)) return ug_fail(who, "null reference, table, sites or count");
-  if ((rc = check_batch_arrays(b, who))) return rc;
+  if (max_sites < 0) return fail_invalid(who, "max_sites " + std::to_string(max_sites));
+  if (!n_sites || !table || (w->len > 0 && !ref) || (max_sites > 0 && !sites)) return fail_invalid(who, "null reference, table, sites or count");
+  if ((rc = check_batch_offsets(b, who))) return rc;
   const int64_t n = b->n;
   // what the rules refuse, before any device work
   int64_t last = -1, last_pos = 0;
   for (int64_t r = 0; r < n; ++r) {
     if (b->ref_id[r] != w->ref_id) continue;
     if (last >= 0 && b->pos[r] < last_pos)
-      return ug_fail(who, "record " + std::to_string(r) + " at position " + std::to_string(b->pos[r]) + " follows record " +
-                              std::to_string(last) + " at " + std::to_string(last_pos) + ": positions decrease");
+      return fail_invalid(who, "record " + std::to_string(r) + " at position " + std::to_string(b->pos[r]) + " follows record " +
+                                   std::to_string(last) + " at " + std::to_string(last_pos) + ": positions decrease");
     last = r, last_pos = b->pos[r];
     const int64_t n_ops = b->cigar_off[r + 1] - b->cigar_off[r], L = b->base_off[r + 1] - b->base_off[r];
     if (!ug_counted(b->flag[r], b->ref_id[r], n_ops, b->mapq[r])) continue;
     int64_t covered, ref_len;
     bool beyond;
-    ug_span(b->cigar + b->cigar_off[r], n_ops, b->pos[r], w->contig_len, covered, ref_len, beyond);
-    if (covered != L) return ug_fail(who, "the CIGAR of record " + std::to_string(r) + " does not cover its bases");
-    if (beyond) return ug_fail(who, "record " + std::to_string(r) + " has an aligned base beyond its contig");
+    cigar_span(b->cigar + b->cigar_off[r], n_ops, b->pos[r], w->contig_len, covered, ref_len, beyond);
+    if (covered != L) return fail_invalid(who, "the CIGAR of record " + std::to_string(r) + " does not cover its bases");
+    if (beyond) return fail_invalid(who, "record " + std::to_string(r) + " has an aligned base beyond its contig");
   }
   if (n == 0 || w->len == 0) {
     *n_sites = 0;
@@ -546,51 +476,20 @@ int fcsug_sites(int32_t device, const fcsug_batch* b, const fcsug_params* prm, c
   }
   if ((rc = device_ok(device))) return rc;
   FCS_SET_DEVICE((device));
-  const size_t N = (size_t)n, c_lo = (size_t)b->cigar_off[0], nc = (size_t)b->cigar_off[n] - c_lo;
-  const size_t b_lo = (size_t)b->base_off[0], nb = (size_t)b->base_off[n] - b_lo;
   const int64_t cap = std::min<int64_t>(max_sites, w->len);
-  size_t total = 0;
-  auto add = [&](size_t bytes) {
-    const size_t o = total;
-    total += pad256(bytes);
-    return o;
-  };
-  const size_t oflag = add(2 * N), oref = add(4 * N), opos = add(4 * N), omapq = add(N), oabs = add(N);
-  const size_t ocoff = add(8 * (N + 1)), oboff = add(8 * (N + 1)), ocig = add(4 * nc), oqual = add(nb), obases = add(nb);
-  const size_t oseq = add((size_t)w->len), otab = add(8 * 3 * (size_t)FCSUG_TABLE_ROWS);
-  const size_t in_bytes = total;
-  const size_t oout = add(16);  // n_sites, status
-  const size_t host_bytes = total;
-  const size_t osites = add(sizeof(fcsug_site) * (size_t)cap), ows = add(ug_workspace(n, w->len).bytes);
+  Arena A;
+  const BatchLayout l = layout_batch(*b, true, A);
+  const size_t oseq = A.add((size_t)w->len), otab = A.add(8 * 3 * (size_t)FCSUG_TABLE_ROWS);
+  const size_t in_bytes = A.total;
+  const size_t oout = A.add(16);  // n_sites, status
+  const size_t host_bytes = A.total;
+  const size_t osites = A.add(sizeof(fcsug_site) * (size_t)cap), ows = A.add(ug_workspace(n, w->len).bytes);
   CallSession S;
-  if ((rc = call_session_acquire(device, host_bytes, total, S))) return rc;
-  Release release{S};
-  std::memcpy(S.host + oflag, b->flag, 2 * N);
-  std::memcpy(S.host + oref, b->ref_id, 4 * N);
-  std::memcpy(S.host + opos, b->pos, 4 * N);
-  std::memcpy(S.host + omapq, b->mapq, N);
-  std::memcpy(S.host + oabs, b->qual_absent, N);
-  std::memcpy(S.host + ocoff, b->cigar_off, 8 * (N + 1));
-  std::memcpy(S.host + oboff, b->base_off, 8 * (N + 1));
-  if (nc) std::memcpy(S.host + ocig, b->cigar + c_lo, 4 * nc);
-  if (nb) std::memcpy(S.host + oqual, b->qual + b_lo, nb), std::memcpy(S.host + obases, b->bases + b_lo, nb);
+  if ((rc = call_session_acquire(device, host_bytes, A.total, S))) return rc;
+  CallLease lease{S};
+  const fcsug_batch d = stage_batch(*b, l, S.host, S.dev);
   std::memcpy(S.host + oseq, ref, (size_t)w->len);
   std::memcpy(S.host + otab, table, 8 * 3 * (size_t)FCSUG_TABLE_ROWS);
-  // the device view keeps the caller's offsets: its CIGAR, base and quality bases are shifted down by the first ones
-  fcsug_batch d;
-  d.n = n;
-  d.flag = reinterpret_cast<const uint16_t*>(S.dev + oflag);
-  d.ref_id = reinterpret_cast<const int32_t*>(S.dev + oref);
-  d.pos = reinterpret_cast<const int32_t*>(S.dev + opos);
-  d.mapq = reinterpret_cast<const uint8_t*>(S.dev + omapq);
-  d.cigar = reinterpret_cast<const uint32_t*>(S.dev + ocig) - c_lo;
-  d.cigar_off = reinterpret_cast<const int64_t*>(S.dev + ocoff);
-  d.n_cigar = b->cigar_off[n];
-  d.bases = reinterpret_cast<const uint8_t*>(S.dev + obases) - b_lo;
-  d.qual = reinterpret_cast<const uint8_t*>(S.dev + oqual) - b_lo;
-  d.base_off = reinterpret_cast<const int64_t*>(S.dev + oboff);
-  d.n_bases = b->base_off[n];
-  d.qual_absent = reinterpret_cast<const uint8_t*>(S.dev + oabs);
   int64_t* dn = reinterpret_cast<int64_t*>(S.dev + oout);
   int32_t* status = reinterpret_cast<int32_t*>(S.dev + oout + 8);
   fcsug_site* dsites = reinterpret_cast<fcsug_site*>(S.dev + osites);
@@ -606,7 +505,7 @@ int fcsug_sites(int32_t device, const fcsug_batch* b, const fcsug_params* prm, c
   std::memcpy(&found, S.host + oout, sizeof found);
   std::memcpy(&st, S.host + oout + 8, sizeof st);
   if ((st & FCSUG_STATUS_SITES) || found > max_sites)
-    return ug_fail(who, "the window has " + std::to_string(found) + " sites, max_sites is " + std::to_string(max_sites));
+    return fail_invalid(who, "the window has " + std::to_string(found) + " sites, max_sites is " + std::to_string(max_sites));
   if (st) return fail(FCS_ERR_DEVICE, "[E::fcsug_sites] the device clamped a checked field (status " + std::to_string(st) + ")");
   if (found > 0) {
     FCS_HIP_CHECK(hipMemcpyAsync(sites, dsites, sizeof(fcsug_site) * (size_t)found, hipMemcpyDeviceToHost, S.s));

@@ -5,16 +5,17 @@
 // take a base.  Every value is an integer.
 //
 //   ug_counted   the record filter (ref_id, CIGAR, flags, MAPQ 255)
-//   ug_span      the read bases the CIGAR covers and the reference span
-//   ug_locus     whether read base i is aligned (M / = / X), and where
 //   ug_qe        the effective quality min(q, MAPQ, 93)
 //   ug_code      the letter code of a read or reference byte (A C G T = 0 .. 3, else 4)
 //   ug_is_site   the site predicate
 //   ug_alt       the alt choice
 //   ug_gl        the three genotype sums
+// The CIGAR walks (cigar_span, cigar_site) are cigar_walk.h's.
 #pragma once
 
 #include <stdint.h>
+
+#include "cigar_walk.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -31,45 +32,6 @@ constexpr int kUgStatusField = 1, kUgStatusRef = 2, kUgStatusOrder = 4, kUgStatu
 
 UG_HD bool ug_counted(uint16_t flag, int32_t ref_id, int64_t n_ops, uint8_t mapq) {
   return ref_id >= 0 && n_ops > 0 && (flag & kUgFlagFilter) == 0 && mapq != 255;
-}
-
-// One pass over the record's n_ops CIGAR words (len << 4 | op): the read bases
-// of S / M / I / = / X, the reference bases of M / D / N / = / X, and whether an
-// aligned base lies outside [0, clen) when the record starts at pos.
-UG_HD void ug_span(const uint32_t* cigar, int64_t n_ops, int64_t pos, int64_t clen, int64_t& covered, int64_t& ref_len,
-                   bool& beyond) {
-  covered = ref_len = 0;
-  beyond = false;
-  for (int64_t k = 0; k < n_ops; ++k) {
-    const uint32_t op = cigar[k] & 15u;
-    const int64_t len = (int64_t)(cigar[k] >> 4);
-    if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) covered += len;
-    if ((op == 0u || op == 7u || op == 8u) && len > 0 && (pos + ref_len < 0 || pos + ref_len + len > clen)) beyond = true;
-    if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) ref_len += len;
-  }
-}
-
-// Read base i (0 <= i < covered): true, with its reference position in p, when it lies in M, = or X.
-UG_HD bool ug_locus(const uint32_t* cigar, int64_t n_ops, int64_t pos, int64_t i, int64_t& p) {
-  int64_t q = 0, r = pos;
-  for (int64_t k = 0; k < n_ops; ++k) {
-    const uint32_t op = cigar[k] & 15u;
-    const int64_t len = (int64_t)(cigar[k] >> 4);
-    if (op == 0u || op == 7u || op == 8u) {
-      if (i < q + len) {
-        p = r + (i - q);
-        return true;
-      }
-      q += len, r += len;
-    } else if (op == 1u || op == 4u) {
-      if (i < q + len) break;
-      q += len;
-    } else if (op == 2u || op == 3u) {
-      r += len;
-    }
-  }
-  p = 0;
-  return false;
 }
 
 UG_HD int ug_qe(int q, int mapq) {

@@ -3,13 +3,10 @@
 // bqsr.chunk_records, the flattening, and the device calls or the host rules.
 #include "bqsr_run.h"
 
-#include <dlfcn.h>
-
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
-#include <mutex>
 #include <sstream>
 #include <unordered_map>
 
@@ -20,6 +17,7 @@
 #include "config.h"
 #include "fasta.h"
 #include "fcship.h"
+#include "flat_batch.h"
 #include "intervals.h"
 
 namespace fcsg {
@@ -27,39 +25,24 @@ namespace fcsg {
 namespace {
 
 struct BqApi {
-  decltype(&fcsbq_ref_create) ref_create = nullptr;
-  decltype(&fcsbq_ref_destroy) ref_destroy = nullptr;
-  decltype(&fcsbq_count) count = nullptr;
-  decltype(&fcsbq_apply) apply = nullptr;
-  const char* (*last_error)() = nullptr;
+  decltype(&fcsbq_ref_create) ref_create = FCSG_DEVICE_ENTRY(fcsbq_ref_create);
+  decltype(&fcsbq_ref_destroy) ref_destroy = FCSG_DEVICE_ENTRY(fcsbq_ref_destroy);
+  decltype(&fcsbq_count) count = FCSG_DEVICE_ENTRY(fcsbq_count);
+  decltype(&fcsbq_apply) apply = FCSG_DEVICE_ENTRY(fcsbq_apply);
+  LastErrorFn last_error = last_error_entry();
 };
 
 const BqApi& bq_api() {
-  static const BqApi A = [] {
-    BqApi a;
-    a.ref_create = reinterpret_cast<decltype(a.ref_create)>(dlsym(RTLD_DEFAULT, "fcsbq_ref_create"));
-    a.ref_destroy = reinterpret_cast<decltype(a.ref_destroy)>(dlsym(RTLD_DEFAULT, "fcsbq_ref_destroy"));
-    a.count = reinterpret_cast<decltype(a.count)>(dlsym(RTLD_DEFAULT, "fcsbq_count"));
-    a.apply = reinterpret_cast<decltype(a.apply)>(dlsym(RTLD_DEFAULT, "fcsbq_apply"));
-    a.last_error = reinterpret_cast<decltype(a.last_error)>(dlsym(RTLD_DEFAULT, "fcs_last_error"));
-    return a;
-  }();
+  static const BqApi A;
   return A;
 }
 
 // The device the job runs on, or -1 (with one log line when the library lacks the entry points).
 int device_of(const BqsrJob& job) {
-  if (job.device < 0) return -1;
-  if (gpu_bqsr_available()) return job.device;
-  static std::once_flag said;
-  std::call_once(said, [] {
-    std::fprintf(stderr, "[fcs-genome bqsr] bqsr.gpu: the loaded libfcship has no fcsbq_count entry point; "
-                         "qualities are recalibrated on the host\n");
-  });
-  return -1;
+  return device_or_host(job.device, gpu_bqsr_available(),
+                        "[fcs-genome bqsr] bqsr.gpu: the loaded libfcship has no fcsbq_count entry point; "
+                        "qualities are recalibrated on the host\n");
 }
-
-int host_threads() { return (int)std::min<unsigned>(host_cpus(), 16); }
 
 // The input's BAM files: the file itself, or a directory's part BAMs in name order.
 std::vector<std::string> input_bams(const std::string& input) {
@@ -191,48 +174,15 @@ Regions load_regions(const std::string& path, const BamHeader& h) {
   return rg;
 }
 
-// One chunk of records as an fcsbq_batch over its own arrays, in the order `order`.
-struct FlatBatch {
-  std::vector<uint16_t> flag;
-  std::vector<int32_t> ref_id, pos, rg;
-  std::vector<uint8_t> mapq, absent, bases, qual;
-  std::vector<uint32_t> cigar;
-  std::vector<int64_t> cigar_off, base_off;
-  fcsbq_batch view() const {
-    fcsbq_batch b;
-    b.n = (int64_t)flag.size();
-    b.flag = flag.data(), b.ref_id = ref_id.data(), b.pos = pos.data(), b.mapq = mapq.data(), b.rg = rg.data();
-    b.cigar = cigar.data(), b.cigar_off = cigar_off.data(), b.n_cigar = (int64_t)cigar.size();
-    b.bases = bases.data(), b.qual = qual.data(), b.base_off = base_off.data(), b.n_bases = (int64_t)bases.size();
-    b.qual_absent = absent.data();
-    return b;
-  }
-};
-
-void flatten(const std::vector<BamRecord>& recs, const std::vector<int32_t>& rg, const std::vector<uint32_t>& order,
-             FlatBatch& f) {
-  const size_t n = order.size();
-  f.flag.resize(n), f.ref_id.resize(n), f.pos.resize(n), f.rg.resize(n), f.mapq.resize(n), f.absent.resize(n);
-  f.cigar_off.assign(n + 1, 0), f.base_off.assign(n + 1, 0);
-  for (size_t k = 0; k < n; ++k) {
-    const BamRecord& r = recs[order[k]];
-    f.flag[k] = r.flag, f.ref_id[k] = r.ref_id, f.pos[k] = r.pos, f.rg[k] = rg[order[k]], f.mapq[k] = r.mapq;
-    f.absent[k] = r.qual.size() != r.seq.size() || r.seq.empty();
-    f.cigar_off[k + 1] = f.cigar_off[k] + (int64_t)r.cigar.size();
-    f.base_off[k + 1] = f.base_off[k] + (int64_t)r.seq.size();
-  }
-  f.cigar.resize((size_t)f.cigar_off[n]);
-  f.bases.resize((size_t)f.base_off[n]);
-  f.qual.resize((size_t)f.base_off[n]);
-  parallel_for(n, host_threads(), [&](size_t k) {
-    const BamRecord& r = recs[order[k]];
-    if (!r.cigar.empty()) std::memcpy(f.cigar.data() + f.cigar_off[k], r.cigar.data(), 4 * r.cigar.size());
-    if (!r.seq.empty()) {
-      std::memcpy(f.bases.data() + f.base_off[k], r.seq.data(), r.seq.size());
-      if (f.absent[k]) std::memset(f.qual.data() + f.base_off[k], 0xff, r.seq.size());
-      else std::memcpy(f.qual.data() + f.base_off[k], r.qual.data(), r.seq.size());
-    }
-  });
+// One chunk of records in the order `order` as an fcsbq_batch over f and its own read groups.
+fcsbq_batch flat_view(const std::vector<BamRecord>& recs, const std::vector<int32_t>& rg, const std::vector<uint32_t>& order,
+                      FlatRecords& f, std::vector<int32_t>& flat_rg) {
+  flatten(recs, order.size(), true, f, order.data());
+  flat_rg.resize(order.size());
+  for (size_t k = 0; k < order.size(); ++k) flat_rg[k] = rg[order[k]];
+  fcsbq_batch b = f.view<fcsbq_batch>(0, order.size());
+  b.rg = flat_rg.data();
+  return b;
 }
 
 // The job's input, read chunk by chunk: the records -L keeps, with their read group indices.
@@ -316,13 +266,13 @@ void count_pass(const BqsrJob& job, int device, CountTables& t, std::vector<std:
   std::vector<BamRecord> recs;
   std::vector<int32_t> rg;
   std::vector<uint32_t> order;
-  FlatBatch f;
+  FlatRecords f;
+  std::vector<int32_t> flat_rg;
   while (in.next(recs, rg)) {
     order.resize(recs.size());
     for (size_t i = 0; i < order.size(); ++i) order[i] = (uint32_t)i;
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rg[a] < rg[b]; });
-    flatten(recs, rg, order, f);
-    const fcsbq_batch b = f.view();
+    const fcsbq_batch b = flat_view(recs, rg, order, f, flat_rg);
     for (int64_t r = 0; r < b.n; ++r)
       st.counted += b.rg[r] >= 0 && !b.qual_absent[r] && !(b.flag[r] & 0x704) && b.mapq[r] != 0 && b.mapq[r] != 255;
     st.records += b.n;
@@ -346,13 +296,13 @@ void apply_pass(const BqsrJob& job, int device, const BqTables& tables, BqsrStat
   std::vector<uint32_t> order;
   std::vector<uint8_t> out;
   std::vector<const BamRecord*> ptrs;
-  FlatBatch f;
+  FlatRecords f;
+  std::vector<int32_t> flat_rg;
   st.records = 0;
   while (in.next(recs, rg)) {
     order.resize(recs.size());
     for (size_t i = 0; i < order.size(); ++i) order[i] = (uint32_t)i;
-    flatten(recs, rg, order, f);
-    const fcsbq_batch b = f.view();
+    const fcsbq_batch b = flat_view(recs, rg, order, f, flat_rg);
     out.assign((size_t)b.n_bases + 1, 0);
     if (device >= 0) {
       if (bq_api().apply(device, &b, tables.n_rg, tables.base.data(), tables.dctx.data(), tables.dcyc.data(), out.data()) != FCS_OK)

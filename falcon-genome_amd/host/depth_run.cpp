@@ -5,8 +5,6 @@
 // summarised and written once the stream has passed its end.
 #include "depth_run.h"
 
-#include <dlfcn.h>
-
 #include <algorithm>
 #include <climits>
 #include <cstdio>
@@ -14,7 +12,6 @@
 #include <fstream>
 #include <map>
 #include <memory>
-#include <mutex>
 #include <set>
 #include <sstream>
 
@@ -24,6 +21,7 @@
 #include "depth.h"
 #include "fasta.h"
 #include "fcship.h"
+#include "flat_batch.h"
 #include "intervals.h"
 
 namespace fcsg {
@@ -31,35 +29,15 @@ namespace fcsg {
 namespace {
 
 struct DpApi {
-  decltype(&fcsdp_count) count = nullptr;
-  decltype(&fcsdp_stats) stats = nullptr;
-  const char* (*last_error)() = nullptr;
+  decltype(&fcsdp_count) count = FCSG_DEVICE_ENTRY(fcsdp_count);
+  decltype(&fcsdp_stats) stats = FCSG_DEVICE_ENTRY(fcsdp_stats);
+  LastErrorFn last_error = last_error_entry();
 };
 
 const DpApi& dp_api() {
-  static const DpApi A = [] {
-    DpApi a;
-    a.count = reinterpret_cast<decltype(a.count)>(dlsym(RTLD_DEFAULT, "fcsdp_count"));
-    a.stats = reinterpret_cast<decltype(a.stats)>(dlsym(RTLD_DEFAULT, "fcsdp_stats"));
-    a.last_error = reinterpret_cast<decltype(a.last_error)>(dlsym(RTLD_DEFAULT, "fcs_last_error"));
-    return a;
-  }();
+  static const DpApi A;
   return A;
 }
-
-// The device the job runs on, or -1 (with one log line when the library lacks the entry points).
-int device_of(const DepthJob& job) {
-  if (job.device < 0) return -1;
-  if (gpu_depth_available()) return job.device;
-  static std::once_flag said;
-  std::call_once(said, [] {
-    std::fprintf(stderr, "[fcs-genome depth] depth.gpu: the loaded libfcship has no fcsdp_count entry point; "
-                         "depths are counted on the host\n");
-  });
-  return -1;
-}
-
-int host_threads() { return (int)std::min<unsigned>(host_cpus(), 16); }
 
 struct Part {
   size_t interval;
@@ -71,48 +49,13 @@ struct Window {
   std::vector<Part> parts;
 };
 
-// One chunk of records as an fcsdp_batch over its own arrays.
-struct FlatBatch {
-  std::vector<uint16_t> flag;
-  std::vector<int32_t> ref_id, pos;
-  std::vector<uint8_t> mapq, absent, qual;
-  std::vector<uint32_t> cigar;
-  std::vector<int64_t> cigar_off, base_off, max_end;  // max_end: the running maximum of the records' ends on their contig
-  // Records [lo, hi) as a batch that keeps the chunk's offsets.
-  fcsdp_batch view(size_t lo, size_t hi) const {
-    fcsdp_batch b;
-    b.n = (int64_t)(hi - lo);
-    b.flag = flag.data() + lo, b.ref_id = ref_id.data() + lo, b.pos = pos.data() + lo, b.mapq = mapq.data() + lo;
-    b.cigar = cigar.data(), b.cigar_off = cigar_off.data() + lo, b.n_cigar = (int64_t)cigar.size();
-    b.bases = nullptr, b.qual = qual.data(), b.base_off = base_off.data() + lo, b.n_bases = (int64_t)qual.size();
-    b.qual_absent = absent.data() + lo;
-    return b;
+// max_end[k]: the running maximum of the ends of records [.., k] on their contig.
+void running_max_end(const std::vector<BamRecord>& recs, std::vector<int64_t>& max_end) {
+  max_end.resize(recs.size());
+  for (size_t k = 0; k < recs.size(); ++k) {
+    const int64_t end = recs[k].end();
+    max_end[k] = k > 0 && recs[k - 1].ref_id == recs[k].ref_id ? std::max(max_end[k - 1], end) : end;
   }
-};
-
-void flatten(const std::vector<BamRecord>& recs, FlatBatch& f) {
-  const size_t n = recs.size();
-  f.flag.resize(n), f.ref_id.resize(n), f.pos.resize(n), f.mapq.resize(n), f.absent.resize(n), f.max_end.resize(n);
-  f.cigar_off.assign(n + 1, 0), f.base_off.assign(n + 1, 0);
-  for (size_t k = 0; k < n; ++k) {
-    const BamRecord& r = recs[k];
-    f.flag[k] = r.flag, f.ref_id[k] = r.ref_id, f.pos[k] = r.pos, f.mapq[k] = r.mapq;
-    f.absent[k] = r.qual.size() != r.seq.size() || r.seq.empty();
-    f.cigar_off[k + 1] = f.cigar_off[k] + (int64_t)r.cigar.size();
-    f.base_off[k + 1] = f.base_off[k] + (int64_t)r.seq.size();
-    const int64_t end = r.end();
-    f.max_end[k] = k > 0 && recs[k - 1].ref_id == r.ref_id ? std::max(f.max_end[k - 1], end) : end;
-  }
-  f.cigar.resize((size_t)f.cigar_off[n]);
-  f.qual.resize((size_t)f.base_off[n]);
-  parallel_for(n, host_threads(), [&](size_t k) {
-    const BamRecord& r = recs[k];
-    if (!r.cigar.empty()) std::memcpy(f.cigar.data() + f.cigar_off[k], r.cigar.data(), 4 * r.cigar.size());
-    if (!r.seq.empty()) {
-      if (f.absent[k]) std::memset(f.qual.data() + f.base_off[k], 0xff, r.seq.size());
-      else std::memcpy(f.qual.data() + f.base_off[k], r.qual.data(), r.seq.size());
-    }
-  });
 }
 
 // The sort key of a record: unmapped records without a contig come last.
@@ -120,7 +63,12 @@ std::pair<int64_t, int64_t> key_of(int32_t ref_id, int32_t pos) { return {ref_id
 
 class Run {
  public:
-  explicit Run(const DepthJob& job) : job_(job), device_(device_of(job)), bams_(sorted_bam_inputs(job.input)) {
+  explicit Run(const DepthJob& job)
+      : job_(job),
+        device_(device_or_host(job.device, gpu_depth_available(),
+                               "[fcs-genome depth] depth.gpu: the loaded libfcship has no fcsdp_count entry point; "
+                               "depths are counted on the host\n")),
+        bams_(sorted_bam_inputs(job.input)) {
     reader_.reset(new BamReader(bams_[0]));
     header_ = reader_->header();
     st_.sample = single_sample(header_, "depth");
@@ -174,11 +122,13 @@ class Run {
   // The chunks in order: each is counted into the windows it overlaps, and every window the stream has passed is finished.
   void stream() {
     std::vector<BamRecord> recs;
-    FlatBatch f;
+    FlatRecords f;
+    std::vector<int64_t> max_end;
     while (next_chunk(recs)) {
       st_.records += (int64_t)recs.size();
-      flatten(recs, f);
-      count_chunk(f);
+      flatten(recs, recs.size(), false, f);
+      running_max_end(recs, max_end);
+      count_chunk(f, max_end);
       const auto last = key_of(f.ref_id.back(), f.pos.back());
       while (cur_ < windows_.size() && (windows_[cur_].w.ref_id < last.first ||
                                         (windows_[cur_].w.ref_id == last.first &&
@@ -248,8 +198,8 @@ class Run {
   }
 
   // The chunk's records given to every window they overlap.
-  void count_chunk(const FlatBatch& f) {
-    const size_t n = f.flag.size();
+  void count_chunk(const FlatRecords& f, const std::vector<int64_t>& max_end) {
+    const size_t n = f.size();
     struct Seg {
       int32_t ref;
       size_t a, b;
@@ -267,16 +217,16 @@ class Run {
       if (si == segs.size()) break;
       if (segs[si].ref > w.ref_id) continue;
       const size_t a = segs[si].a, b = segs[si].b;
-      if (si + 1 == segs.size() && f.max_end[b - 1] <= w.start) break;  // later windows hold nothing of this chunk
+      if (si + 1 == segs.size() && max_end[b - 1] <= w.start) break;  // later windows hold nothing of this chunk
       // the records that start before the window's end and whose running maximum end lies beyond its start
       const size_t hi = (size_t)(std::lower_bound(f.pos.begin() + (long)a, f.pos.begin() + (long)b, w.start + w.len,
                                                   [](int32_t p, int64_t e) { return (int64_t)p < e; }) - f.pos.begin());
-      const size_t lo = (size_t)(std::upper_bound(f.max_end.begin() + (long)a, f.max_end.begin() + (long)hi, w.start) -
-                                 f.max_end.begin());
+      const size_t lo = (size_t)(std::upper_bound(max_end.begin() + (long)a, max_end.begin() + (long)hi, w.start) -
+                                 max_end.begin());
       if (lo >= hi) continue;
       std::vector<uint32_t>& depth = open_[wi];
       if (depth.empty()) depth.assign((size_t)w.len, 0);
-      const fcsdp_batch view = f.view(lo, hi);
+      const fcsdp_batch view = f.view<fcsdp_batch>(lo, hi);
       if (device_ >= 0) {
         if (dp_api().count(device_, &view, &prm_, &w, depth.data()) != FCS_OK)
           throw failedCommand(std::string("[E::fcs-genome depth] fcsdp_count: ") + dp_api().last_error());

@@ -2,19 +2,17 @@
 // the device call or the host rules (markdup.cpp), flags, and the markdup command.
 #include "markdup.h"
 
-#include <dlfcn.h>
-
 #include <algorithm>
 #include <array>
 #include <cstdio>
 #include <cstring>
-#include <mutex>
 #include <sstream>
 #include <string_view>
 #include <unordered_map>
 
 #include "common.h"
 #include "fcship.h"
+#include "flat_batch.h"
 
 namespace fcsg {
 
@@ -46,17 +44,12 @@ std::vector<int32_t> match_mates(const std::vector<BamRecord>& recs) {
 namespace {
 
 struct DupApi {
-  decltype(&fcsdup_mark) mark = nullptr;
-  const char* (*last_error)() = nullptr;
+  decltype(&fcsdup_mark) mark = FCSG_DEVICE_ENTRY(fcsdup_mark);
+  LastErrorFn last_error = last_error_entry();
 };
 
 const DupApi& dup_api() {
-  static const DupApi A = [] {
-    DupApi a;
-    a.mark = reinterpret_cast<decltype(a.mark)>(dlsym(RTLD_DEFAULT, "fcsdup_mark"));
-    a.last_error = reinterpret_cast<decltype(a.last_error)>(dlsym(RTLD_DEFAULT, "fcs_last_error"));
-    return a;
-  }();
+  static const DupApi A;
   return A;
 }
 
@@ -80,7 +73,7 @@ MarkdupStats mark_duplicates(std::vector<BamRecord>& recs, const std::vector<int
   }
   std::vector<uint32_t> cigar((size_t)cigar_off[n]);
   std::vector<uint8_t> qual((size_t)qual_off[n]);
-  parallel_for(n, (int)std::min<unsigned>(host_cpus(), 16), [&](size_t r) {
+  parallel_for(n, host_threads(), [&](size_t r) {
     if (!recs[r].cigar.empty()) std::memcpy(cigar.data() + cigar_off[r], recs[r].cigar.data(), 4 * recs[r].cigar.size());
     if (!recs[r].qual.empty()) std::memcpy(qual.data() + qual_off[r], recs[r].qual.data(), recs[r].qual.size());
   });
@@ -92,15 +85,10 @@ MarkdupStats mark_duplicates(std::vector<BamRecord>& recs, const std::vector<int
   b.n_ref = n_ref, b.n_lib = n_lib;
   std::vector<uint8_t> dup(n, 0);
   MarkdupStats st;
-  bool on_device = device >= 0;
-  if (on_device && !gpu_markdup_available()) {
-    static std::once_flag said;
-    std::call_once(said, [] {
-      std::fprintf(stderr, "[fcs-genome markdup] markdup.gpu: the loaded libfcship has no fcsdup_mark entry point; "
-                           "duplicates are marked on the host\n");
-    });
-    on_device = false;
-  }
+  const bool on_device =
+      device_or_host(device, gpu_markdup_available(),
+                     "[fcs-genome markdup] markdup.gpu: the loaded libfcship has no fcsdup_mark entry point; "
+                     "duplicates are marked on the host\n") >= 0;
   if (on_device) {
     fcsdup_stats ds;
     if (dup_api().mark(device, &b, dup.data(), &ds) != FCS_OK)

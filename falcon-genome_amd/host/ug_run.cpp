@@ -5,15 +5,12 @@
 // record is given to every window it overlaps.
 #include "ug_run.h"
 
-#include <dlfcn.h>
-
 #include <algorithm>
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <mutex>
 
 #include "bam.h"
 #include "common.h"
@@ -21,6 +18,7 @@
 #include "depth_run.h"
 #include "fasta.h"
 #include "fcship.h"
+#include "flat_batch.h"
 #include "ug.h"
 #include "vcf.h"
 
@@ -29,30 +27,13 @@ namespace fcsg {
 namespace {
 
 struct UgApi {
-  decltype(&fcsug_sites) sites = nullptr;
-  const char* (*last_error)() = nullptr;
+  decltype(&fcsug_sites) sites = FCSG_DEVICE_ENTRY(fcsug_sites);
+  LastErrorFn last_error = last_error_entry();
 };
 
 const UgApi& ug_api() {
-  static const UgApi A = [] {
-    UgApi a;
-    a.sites = reinterpret_cast<decltype(a.sites)>(dlsym(RTLD_DEFAULT, "fcsug_sites"));
-    a.last_error = reinterpret_cast<decltype(a.last_error)>(dlsym(RTLD_DEFAULT, "fcs_last_error"));
-    return a;
-  }();
+  static const UgApi A;
   return A;
-}
-
-// The device the job runs on, or -1 (with one log line when the library lacks the entry point).
-int device_of(const UgJob& job) {
-  if (job.device < 0) return -1;
-  if (gpu_ug_available()) return job.device;
-  static std::once_flag said;
-  std::call_once(said, [] {
-    std::fprintf(stderr, "[fcs-genome ug] ug.gpu: the loaded libfcship has no fcsug_sites entry point; "
-                         "sites are piled up on the host\n");
-  });
-  return -1;
 }
 
 // A configuration key that holds a number.
@@ -64,8 +45,6 @@ double conf_double(const std::string& key) {
   return d;
 }
 
-int host_threads() { return (int)std::min<unsigned>(host_cpus(), 16); }
-
 struct Part {
   int64_t start, end;  // window offsets
 };
@@ -75,54 +54,17 @@ struct Window {
   std::vector<Part> parts;
 };
 
-// The records of one window as an fcsug_batch over its own arrays.
-struct FlatBatch {
-  std::vector<uint16_t> flag;
-  std::vector<int32_t> ref_id, pos;
-  std::vector<uint8_t> mapq, absent, qual, bases;
-  std::vector<uint32_t> cigar;
-  std::vector<int64_t> cigar_off, base_off;
-  fcsug_batch view() const {
-    fcsug_batch b;
-    b.n = (int64_t)flag.size();
-    b.flag = flag.data(), b.ref_id = ref_id.data(), b.pos = pos.data(), b.mapq = mapq.data();
-    b.cigar = cigar.data(), b.cigar_off = cigar_off.data(), b.n_cigar = (int64_t)cigar.size();
-    b.bases = bases.data(), b.qual = qual.data(), b.base_off = base_off.data(), b.n_bases = (int64_t)qual.size();
-    b.qual_absent = absent.data();
-    return b;
-  }
-};
-
-void flatten(const std::vector<BamRecord>& recs, size_t n, FlatBatch& f) {
-  f.flag.resize(n), f.ref_id.resize(n), f.pos.resize(n), f.mapq.resize(n), f.absent.resize(n);
-  f.cigar_off.assign(n + 1, 0), f.base_off.assign(n + 1, 0);
-  for (size_t k = 0; k < n; ++k) {
-    const BamRecord& r = recs[k];
-    f.flag[k] = r.flag, f.ref_id[k] = r.ref_id, f.pos[k] = r.pos, f.mapq[k] = r.mapq;
-    f.absent[k] = r.qual.size() != r.seq.size() || r.seq.empty();
-    f.cigar_off[k + 1] = f.cigar_off[k] + (int64_t)r.cigar.size();
-    f.base_off[k + 1] = f.base_off[k] + (int64_t)r.seq.size();
-  }
-  f.cigar.resize((size_t)f.cigar_off[n]);
-  f.qual.resize((size_t)f.base_off[n]);
-  f.bases.resize((size_t)f.base_off[n]);
-  parallel_for(n, host_threads(), [&](size_t k) {
-    const BamRecord& r = recs[k];
-    if (!r.cigar.empty()) std::memcpy(f.cigar.data() + f.cigar_off[k], r.cigar.data(), 4 * r.cigar.size());
-    if (!r.seq.empty()) {
-      std::memcpy(f.bases.data() + f.base_off[k], r.seq.data(), r.seq.size());
-      if (f.absent[k]) std::memset(f.qual.data() + f.base_off[k], 0xff, r.seq.size());
-      else std::memcpy(f.qual.data() + f.base_off[k], r.qual.data(), r.seq.size());
-    }
-  });
-}
-
 // The sort key of a record: unmapped records without a contig come last.
 std::pair<int64_t, int64_t> key_of(int32_t ref_id, int32_t pos) { return {ref_id < 0 ? (int64_t)INT32_MAX + 1 : ref_id, pos}; }
 
 class Run {
  public:
-  explicit Run(const UgJob& job) : job_(job), device_(device_of(job)), bams_(sorted_bam_inputs(job.input)) {
+  explicit Run(const UgJob& job)
+      : job_(job),
+        device_(device_or_host(job.device, gpu_ug_available(),
+                               "[fcs-genome ug] ug.gpu: the loaded libfcship has no fcsug_sites entry point; "
+                               "sites are piled up on the host\n")),
+        bams_(sorted_bam_inputs(job.input)) {
     reader_.reset(new BamReader(bams_[0]));
     header_ = reader_->header();
     st_.sample = single_sample(header_, "ug");
@@ -156,7 +98,7 @@ class Run {
       std::vector<std::pair<std::string, int64_t>> contigs;
       for (size_t k = 0; k < header_.names.size(); ++k) contigs.emplace_back(header_.names[k], header_.lengths[k]);
       VcfWriter out(job_.output, ug_vcf_header(st_.sample, contigs));
-      FlatBatch f;
+      FlatRecords f;
       for (const Window& win : windows_) {
         call_window(win, f, out);
         if (interrupted()) throw interruptedError();
@@ -223,7 +165,7 @@ class Run {
     }
   }
 
-  void call_window(const Window& win, FlatBatch& f, VcfWriter& out) {
+  void call_window(const Window& win, FlatRecords& f, VcfWriter& out) {
     const fcsug_window& w = win.w;
     const std::pair<int64_t, int64_t> past{w.ref_id, w.start + w.len};
     // records the stream has left behind: earlier contigs, and those that end before the window's start
@@ -240,8 +182,8 @@ class Run {
     size_t n = 0;
     while (n < buf_.size() && key_of(buf_[n].ref_id, buf_[n].pos) < past) ++n;
     if (n == 0) return;
-    flatten(buf_, n, f);
-    const fcsug_batch view = f.view();
+    flatten(buf_, n, true, f);
+    const fcsug_batch view = f.view<fcsug_batch>(0, n);
     const uint8_t* ref = reinterpret_cast<const uint8_t*>(contigs_[(size_t)w.ref_id].data()) + w.start;
     std::vector<fcsug_site> host_sites;
     const fcsug_site* sites = nullptr;

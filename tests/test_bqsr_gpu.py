@@ -100,6 +100,29 @@ def test_lengths_at_every_offset_residue(gpu, world):
         assert device_apply(records, hand, gpu, first_offset=first) == B.apply(records, *hand)
 
 
+def test_junk_before_the_first_cigar_word_and_the_first_base(gpu, hand_ref):
+    """Both offset arrays start at 3: only [off[0], off[n]) is staged and the device view keeps the caller's offsets."""
+    records = [r for k in (0, 1, 2, 3, 5, 12) for r in CASES[k]["records"]]   # clips, known sites, two read groups
+    assert len(records) == 12
+    plain = fcship.bq_arrays(*B.flatten(records))
+    flag, ref_id, pos, mapq, rg, cigar, cigar_off, bases, qual, base_off, absent = plain
+    junk = np.array([0xEE] * 3, np.uint8)
+    padded = (flag, ref_id, pos, mapq, rg, np.concatenate([np.full(3, 0xEEEEEEEE, np.uint32), cigar]), cigar_off + 3,
+              np.concatenate([junk, bases]), np.concatenate([junk, qual]), base_off + 3, absent)
+    assert len(padded[5]) == len(cigar) + 3 and len(padded[7]) == len(padded[8]) == len(bases) + 3
+    rctx, rcyc = B.new_tables(2)
+    B.count(records, B.REFS, B.KNOWN, 2, rctx, rcyc)
+    ctx, cyc = fcship.bq_count(hand_ref, padded, 2)
+    assert (ctx == rctx).all() and (cyc == rcyc).all() and cyc.sum() > 0
+    pctx, pcyc = fcship.bq_count(hand_ref, plain, 2)
+    assert ctx.tobytes() == pctx.tobytes() and cyc.tobytes() == pcyc.tobytes()
+    tables = B.hand_table(2)
+    out = fcship.bq_apply(padded, *tables, device=gpu)
+    assert (out[:3] == 0xEE).all()
+    assert B.unflatten_quals(records, out, 3) == B.apply(records, *tables)
+    assert out[3:].tobytes() == fcship.bq_apply(plain, *tables, device=gpu).tobytes()
+
+
 def test_20000_copies_of_one_read_at_one_quality(gpu, hand_ref):
     records = B.one_hot_read(20000)
     rctx, rcyc = B.new_tables(1)

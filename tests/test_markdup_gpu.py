@@ -48,6 +48,21 @@ def test_all_hand_cases_as_one_batch(gpu):
     assert check(records, gpu) == [f for _, _, want in CASES for f in want]
 
 
+def test_junk_before_the_first_cigar_word_and_the_first_quality_byte(gpu):
+    """Both offset arrays start at 3: only [off[0], off[n]) is staged and the device view keeps the caller's offsets."""
+    records = []
+    for k, (_, recs, _) in enumerate(CASES):
+        base = len(records)
+        records += [dict(r, pos=r["pos"] + 3000 * (k + 1), mate=r["mate"] + base if r["mate"] >= 0 else -1) for r in recs]
+    flag, ref_id, pos, mate, lib, cigar, cigar_off, qual, qual_off = M.flatten(records)
+    padded = (flag, ref_id, pos, mate, lib, np.concatenate([np.full(3, 0xEEEEEEEE, np.uint32), cigar]), cigar_off + 3,
+              np.concatenate([np.full(3, 0xEE, np.uint8), qual]), qual_off + 3)
+    n_ref, n_lib = M.n_ref_lib(records)
+    dup, st = fcship.dup_mark(padded, n_ref, n_lib, device=gpu)
+    assert list(dup) == M.expected(records) == [f for _, _, want in CASES for f in want]
+    assert st == M.stats(records)
+
+
 def test_zero_one_and_two_records(gpu):
     assert device_mark([], gpu) == ([], dict(examined=0, pairs=0, fragments=0, duplicates=0))
     assert check([M.rec(0, 0, 5, "10M", 30)], gpu) == [0]

@@ -102,7 +102,7 @@ void count_shared(const fcsdp_batch& b, const fcsdp_params& prm, const fcsdp_win
     const int64_t n_ops = b.cigar_off[r + 1] - b.cigar_off[r], L = b.base_off[r + 1] - b.base_off[r];
     if (!dp_counted(b.flag[r], b.ref_id[r], n_ops, b.mapq[r], prm.min_mapq, prm.max_mapq)) continue;
     int64_t covered, ref_len;
-    dp_span(cigar, n_ops, covered, ref_len);
+    cigar_span(cigar, n_ops, covered, ref_len);
     if (covered != L) continue;
     const bool absent = b.qual_absent[r] != 0;
     const uint8_t* qual = b.qual + b.base_off[r];
@@ -113,7 +113,7 @@ void count_shared(const fcsdp_batch& b, const fcsdp_params& prm, const fcsdp_win
         const int64_t i = i0 + lane;
         int64_t p;
         off[lane] = -1;
-        if (i < L && dp_site(cigar, n_ops, b.pos[r], i, p) && p >= 0 && p < w.contig_len &&
+        if (i < L && cigar_site(cigar, n_ops, b.pos[r], i, p) && p >= 0 && p < w.contig_len &&
             dp_base_ok(absent ? 0 : qual[i], prm.min_baseq, prm.max_baseq))
           off[lane] = dp_in_window(p, w.start, w.len, w.contig_len);
         if (off[lane] >= 0) counted |= 1ull << lane;

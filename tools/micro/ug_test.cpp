@@ -126,7 +126,7 @@ std::vector<fcsug_site> sites_shared(const fcsug_batch& b, const fcsug_params& p
     if (!ug_counted(b.flag[r], b.ref_id[r], n_ops, b.mapq[r])) continue;
     int64_t covered, ref_len;
     bool beyond;
-    ug_span(b.cigar + b.cigar_off[r], n_ops, b.pos[r], w.contig_len, covered, ref_len, beyond);
+    cigar_span(b.cigar + b.cigar_off[r], n_ops, b.pos[r], w.contig_len, covered, ref_len, beyond);
     if (covered == b.base_off[r + 1] - b.base_off[r]) end[(size_t)r] = b.pos[r] + ref_len;
   }
   std::vector<fcsug_site> out;
@@ -142,7 +142,7 @@ std::vector<fcsug_site> sites_shared(const fcsug_batch& b, const fcsug_params& p
         for (int lane = 0; lane < 64; ++lane) {
           const int64_t i = i0 + lane;
           int64_t p;
-          if (!(i < L && ug_locus(cigar, n_ops, b.pos[r], i, p) && p >= s && p < e)) continue;
+          if (!(i < L && cigar_site(cigar, n_ops, b.pos[r], i, p) && p >= s && p < e)) continue;
           const int x = ug_code(b.bases[b.base_off[r] + i]);
           const int qe = ug_qe(b.qual_absent[r] ? 0 : b.qual[b.base_off[r] + i], mapq);
           if (x > 3 || qe < prm.min_baseq) continue;
