@@ -7,29 +7,48 @@
 // cell, of which the steady steps are 7.5).  Here the roles are transposed:
 //   * lane l of a 16-lane segment OWNS the haplotype columns l*C + 1 ..
 //     l*C + C (C per launch class, H <= 16 C - 1) and keeps their state in
-//     registers: X(r, c) (the diagonal hand-off M*mm' + I*gm' + D*gm') and
-//     I(r + 1, c) of the row it finished last;
+//     registers: X~(r, c) (the diagonal hand-off M*mm' + I*gm' + D*gm' divided
+//     by mm', see the cell below) and I(r + 1, c) of the row it finished last;
 //   * each step the lane runs ONE read row across its C columns (row g = t - l
 //     of the segment's row stream: one row of skew per lane), so a step is C
 //     cells of straight-line code with no per-cell lane traffic: the only
-//     cross-lane values are the lane below's X(g - 1, l*C) and the deletion
-//     chain D entering column l*C + 1 (two DPP row_shr:1 per value);
+//     cross-lane values are the lane below's X~(g - 1, l*C) and the deletion
+//     chain E entering column l*C + 1 (two DPP row_shr:1 per value);
 //   * the two halves of every packed register are two INDEPENDENT pairs
-//     ("half-streams" A and B), so all seven FP ops of a cell are v_pk_*_f32
+//     ("half-streams" A and B), so all six FP ops of a cell are v_pk_*_f32
 //     on two cells, with no swaps;
-//   * row parameters (8 per row and half) come from a 32-row LDS ring that the
+//   * row parameters (7 per row and half) come from a 32-row LDS ring that the
 //     segment's 16 lanes fill 8 rows ahead (one (row, half) item per lane every
 //     8 steps): no per-stripe setup.
 // Each half-stream runs K pairs back to back as one row stream per pair
 // [rows 1..R, V, Z]: V sums the last row (as in phmm3: prior 1 on the
-// haplotype's columns and on column H + 1, 0 past it, D = running sum), and
-// Z resets every column to the row-0 boundary of the next pair (X = 1 with
-// row 1's priors pre-multiplied by (2^120 / H) * gm_1, I = 0) through a D
+// haplotype's columns and on column H + 1, 0 past it, E = running sum), and
+// Z resets every column to the row-0 boundary of the next pair (X~ = 1 with
+// row 1's priors pre-multiplied by (2^120 / H) * gm_1, I = 0) through an E
 // chain of ones started at lane 0.  The sum therefore leaves lane 15 as the
-// D entering column 16 C + 1 of the V row: no column search.  There is no
+// E entering column 16 C + 1 of the V row: no column search.  There is no
 // fill or drain inside a stream, only at its end (15 steps per stream).
-// Per cell the arithmetic is phmm3's exactly (same operations, same order),
-// so the results are bitwise those of the row-streamed kernel.
+// The cell is SIX fp32 operations, one fewer than phmm3's:
+//     E  = fma(E(c - 1), yy, M(c - 1))      deletion chain, unit coefficient
+//     M' = X~(r - 1, c) * prior(c + 1)      the next column's match
+//     X~ = fma(E, b, fma(I, a, M))          hand-off, divided by mm'
+//     I' = fma(M, mx, I * xx)
+//   * along a row my and yy are constants, so D = my * E with E = yy * E + M:
+//     a yy-weighted sum of the row's earlier M, bounded by the row's mass;
+//   * X~ = X / mm' with a = gm' / mm' and b = gm' * my / mm' (mm', gm': the
+//     row below's match-to-match and gap-to-match); the row below gets mm'
+//     back in its priors, e1 * mm_own and e3 * mm_own (row 1 keeps (2^120 / H)
+//     * gm_1: mm_1 never enters the recurrence).  Row R hands over M + I
+//     (a = 1, b = 0), V hands over M (a = b = 0), Z gives E = X~ = 1 (yy = b =
+//     1, a = 0, priors 0).
+//   * A row below with mm' < 2^-4 (0 when both indel qualities are <= 3) is a
+//     hazard: its item is built with a = b = 0, so only finite values enter
+//     the stream (a Z row does not clear a NaN), and its pair is flagged in
+//     `other`: the capture hands it to the one-row kernel like a haplotype
+//     byte outside A/C/G/T/N.  With the bound a <= 16 and X~ < 2^125.
+// The sums agree with the row-streamed kernel's to fp32 rounding (about 1e-7
+// relative), no longer bitwise; the three kernels here stay bitwise equal to
+// each other.
 // Three kernels follow.  phmm4_kernel is the one described above, two packed
 // half-streams per register; it stands alone and is kept as the bitwise
 // reference of the other two (FCSHIP_COLS=packed).  phmm5_kernel and
@@ -69,7 +88,7 @@ __host__ __device__ inline int cols_class(int H) {
   return -1;
 }
 // LDS per wave: a 32-row ring per segment of six 16-byte chunks per row:
-// {e1, e3}, {my, yy}, {mm, gm}, {mx, xx} as {A, B} pairs, the match tables
+// {e1, e3}, {b, yy}, {a, -}, {mx, xx} as {A, B} pairs, the match tables
 // {Tlo A, Tlo B, Thi A, Thi B} and the Z flags {A, B, A, B} (floats).  The
 // layout is chunk-major, then segment, then slot (16 B entries): the 16 lanes
 // of a segment read 16 consecutive slots of a chunk, 256 contiguous bytes
@@ -78,7 +97,7 @@ __host__ __device__ inline int cols_class(int H) {
 constexpr int kColsRing = 32;
 constexpr int kColsChunks = 6;
 constexpr int kColsChunkBytes = kColsRing * 4 * 16;  // one chunk of every (slot, segment)
-constexpr int kColsCapOff = kColsChunks * kColsChunkBytes;  // lane 15's D per step of a block
+constexpr int kColsCapOff = kColsChunks * kColsChunkBytes;  // lane 15's E per step of a block
 constexpr int kColsTabOff = kColsCapOff + 4 * 8 * 8;  // ph2pr | dmatch | dmis (3 x 128 floats) for the ring items
 constexpr int kColsLds = kColsTabOff + 3 * 128 * 4;
 
@@ -93,45 +112,58 @@ __device__ __forceinline__ uint32_t vconst(uint32_t k) {
 
 // One (row, half) item of the ring.
 struct ColsItem {
-  float e1, e3, my, yy, mm, gm, mx, xx;
+  float e1, e3, b, yy, a, mx, xx;
   uint32_t tlo, thi;
   float z;
 };
+
+// A row below whose match-to-match is under this bound (both indel qualities
+// <= 3 give exactly 0) cannot be divided out of the hand-off: its pair goes to
+// the one-row kernel.  With it a <= 16, so X~ stays below 2^125 even for H = 1.
+constexpr float kColsMinMm = 0.0625f;
 
 // Roles: 0 = Z (reset row, also before and after the stream), 2 = row r < R,
 // 3 = row R, 4 = V.  Match tables for v_perm on the column codes (A, C, G, T
 // = 0..3 in Tlo, hap N = 4, column H + 1 = 5, past it = 6 in Thi): byte = 1
 // on a match.
-__device__ __forceinline__ ColsItem cols_item(const PhmmTables<float>& tab, const RawRow& raw, int role, bool first,
-                                              float ih) {
+// oiq: the row's own insertion quality (rows >= 2 carry their own match-to-
+// match in the priors: the row above handed X / mm over).  hazard: the row
+// below's match-to-match is under kColsMinMm; the item then holds a = b = 0,
+// so nothing but finite values enters the stream, and the caller flags the pair.
+__device__ __forceinline__ ColsItem cols_item(const PhmmTables<float>& tab, const RawRow& raw, int oiq, int role,
+                                              bool first, float ih, bool& hazard) {
   ColsItem c;
+  hazard = false;
   if (role == 2 || role == 3) {
     const RowP<float> q = row_params<float, false>(tab, raw);
-    const float x0 = first ? ih * tab.dmatch[raw.gq & 127] : 1.f;
+    const int oi = oiq & 127, od = raw.dq & 127;
+    const int hi = oi > od ? oi : od, lo = oi > od ? od : oi;
+    const float x0 = first ? ih * tab.dmatch[raw.gq & 127] : tab.mm[((hi * (hi + 1)) >> 1) + lo];
     const bool last = role == 3;
+    hazard = !last && !(q.mm >= kColsMinMm);
+    const float inv = (last || hazard) ? 0.f : 1.f / q.mm;
     c.e1 = q.e1 * x0;
     c.e3 = q.e3 * x0;
-    c.my = last ? 0.f : q.my;
+    c.b = q.my * inv;  // q.my = my * gm' (row_params)
     c.yy = q.yy;
-    c.mm = last ? 1.f : q.mm;
-    c.gm = last ? 1.f : q.gm;
+    c.a = last ? 1.f : q.gm * inv;
     c.mx = last ? 0.f : q.mx;
     c.xx = last ? 0.f : q.xx;
     const int bc = base_code((unsigned char)raw.rb);
     c.tlo = bc < 4 ? 1u << (8 * bc) : bc == 4 ? vconst(0x01010101u) : 0u;
     c.thi = 0x00000001u;
     c.z = 0.f;
-  } else if (role == 4) {  // V: prior 1 on codes 0..5, 0 past column H + 1; D = running sum of M
+  } else if (role == 4) {  // V: prior 1 on codes 0..5, 0 past column H + 1; E = running sum of M, X~ = M
     c.e1 = 1.f;
     c.e3 = 0.f;
-    c.my = c.yy = c.mm = c.gm = 1.f;
-    c.mx = c.xx = 0.f;
+    c.yy = 1.f;
+    c.a = c.b = c.mx = c.xx = 0.f;
     c.tlo = vconst(0x01010101u);
     c.thi = vconst(0x00000101u);
     c.z = 0.f;
-  } else {  // Z: M = 0, D = 1 (from lane 0's boundary), X = D = 1, I = 0
-    c.e1 = c.e3 = c.my = c.mm = c.gm = c.mx = c.xx = 0.f;
-    c.yy = 1.f;
+  } else {  // Z: M = 0, E = 1 (from lane 0's boundary), X~ = E = 1, I = 0
+    c.e1 = c.e3 = c.a = c.mx = c.xx = 0.f;
+    c.b = c.yy = 1.f;
     c.tlo = c.thi = 0u;
     c.z = 1.f;
   }
@@ -143,10 +175,10 @@ __device__ __forceinline__ void cols_put(unsigned char* smem, int slot, int seg,
   constexpr int F = kColsChunkBytes / 4;  // floats per chunk
   p[0] = c.e1;
   p[2] = c.e3;
-  p[F] = c.my;
+  p[F] = c.b;
   p[F + 2] = c.yy;
-  p[2 * F] = c.mm;
-  p[2 * F + 2] = c.gm;
+  p[2 * F] = c.a;
+  p[2 * F + 2] = 0.f;
   p[3 * F] = c.mx;
   p[3 * F + 2] = c.xx;
   uint32_t* const q = reinterpret_cast<uint32_t*>(p);
@@ -288,7 +320,8 @@ __global__ __launch_bounds__(64, 2) void phmm4_kernel(
     // Haplotype codes per half: cur (in use), nxt (the next pair of the
     // half-stream, taken by lane l at stream row swr[h], i.e. step swr + l),
     // nk[h] = the pair held in nxt.  other[h]: bit k = pair k of the half has
-    // a haplotype byte outside A/C/G/T/N (segment-uniform).
+    // a haplotype byte outside A/C/G/T/N or a read row under kColsMinMm
+    // (segment-uniform).
     uint32_t cur[2][NW], nxt[2][NW];
     int nk[2], swr[2];
     unsigned other[2] = {0u, 0u};
@@ -332,7 +365,7 @@ __global__ __launch_bounds__(64, 2) void phmm4_kernel(
     // later) builds the item from them and writes it.
     int kp = 0;  // stage A's cursor: the pair of half th holding this lane's item row
     RawRow praw{-1, 0, 0, 0, 0, 0, 0};
-    int prole = 0;  // role | first << 4
+    int prole = 0;  // role | first << 4 | the row's own insertion quality << 8
     float pih = 0.f;
     // the cursor pair's table entries, cached: the shuffles run only in the
     // blocks where some lane's cursor moves (about one block in 13 on C2)
@@ -367,13 +400,25 @@ __global__ __launch_bounds__(64, 2) void phmm4_kernel(
       else if (ok && r == R) role = 4;
       prole = role | (r == 0 ? 16 : 0);
       praw = (role == 2 || role == 3) ? load_raw(b, R, ro, r) : RawRow{-1, 0, 0, 0, 0, 0, 0};
+      if (role == 2 || role == 3) prole |= (int)b.iq[ro + r] << 8;
     };
+    // kp is still the cursor stage A left for this item: a hazard row sets its
+    // pair's bit of other[th] in every lane of the segment (rare: one branch).
     auto stage_b = [&](int base) {
+      bool hz;
       cols_put(smem_raw, (base + tk) & (kColsRing - 1), seg, th,
-               cols_item(tab, praw, prole & 15, (prole & 16) != 0, pih));
+               cols_item(tab, praw, prole >> 8, prole & 15, (prole & 16) != 0, pih, hz));
+      if (__ballot(hz) != 0ull) {  // uniform
+        unsigned m = hz ? 1u << (kp + 8 * th) : 0u;
+#pragma unroll
+        for (int d = 1; d < 16; d <<= 1) m |= (unsigned)__shfl_xor((int)m, d, 16);
+        other[0] |= m & 0xFFu;
+        other[1] |= m >> 8;
+      }
     };
     {  // ring prologue: rows -16..-1 are Z (slots 16..31), rows 0..7 built, rows 8..15 requested
-      ColsItem z = cols_item(tab, RawRow{-1, 0, 0, 0, 0, 0, 0}, 0, false, 0.f);
+      bool hz;
+      ColsItem z = cols_item(tab, RawRow{-1, 0, 0, 0, 0, 0, 0}, 0, 0, false, 0.f, hz);
       cols_put(smem_raw, 16 + tk, seg, th, z);
       cols_put(smem_raw, 24 + tk, seg, th, z);
       stage_a(0);
@@ -381,8 +426,8 @@ __global__ __launch_bounds__(64, 2) void phmm4_kernel(
       stage_a(8);
     }
 
-    // Lane state: the columns' X and I after a Z row; the D chain and the
-    // lane below's X as if it had run Z rows.
+    // Lane state: the columns' X~ and I after a Z row; the E chain and the
+    // lane below's X~ as if it had run Z rows.
     pf2 Xn[C], In[C];
 #pragma unroll
     for (int j = 0; j < C; ++j) {
@@ -477,10 +522,10 @@ __global__ __launch_bounds__(64, 2) void phmm4_kernel(
         const u4 cr = *reinterpret_cast<const __attribute__((address_space(3))) u4*>((uintptr_t)(pa + 4 * kColsChunkBytes));
         const pf2 z1 = *reinterpret_cast<const __attribute__((address_space(3))) pf2*>((uintptr_t)(pa + 5 * kColsChunkBytes));
         const pf2 z2 = *reinterpret_cast<const __attribute__((address_space(3))) pf2*>((uintptr_t)(pa + 5 * kColsChunkBytes + 8));
-        const pf2 e1 = pf2{r0.x, r0.y}, e3 = pf2{r0.z, r0.w}, my = pf2{r1.x, r1.y}, yy = pf2{r1.z, r1.w};
-        const pf2 mm = pf2{r2.x, r2.y}, gm = pf2{r2.z, r2.w}, mx = pf2{r3.x, r3.y}, xx = pf2{r3.z, r3.w};
-        // the lane below's D into column l*C + 1 (lane 0: 1 on Z rows, else
-        // 0) and its X(g, l*C) for the next row (lane 0: X(g, 0) = 1 after a Z row)
+        const pf2 e1 = pf2{r0.x, r0.y}, e3 = pf2{r0.z, r0.w}, cb = pf2{r1.x, r1.y}, yy = pf2{r1.z, r1.w};
+        const pf2 ca = pf2{r2.x, r2.y}, mx = pf2{r3.x, r3.y}, xx = pf2{r3.z, r3.w};
+        // the lane below's E into column l*C + 1 (lane 0: 1 on Z rows, else
+        // 0) and its X~(g, l*C) for the next row (lane 0: X~(g, 0) = 1 after a Z row)
         pf2 din, xnx;
         din.x = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(z1.x), __float_as_int(dn.x), kDppRowShr1, 0xF, 0xF, false));
         din.y = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(z1.y), __float_as_int(dn.y), kDppRowShr1, 0xF, 0xF, false));
@@ -490,7 +535,7 @@ __global__ __launch_bounds__(64, 2) void phmm4_kernel(
         xin = xnx;
         uint32_t mA = 0, mB = 0;
         // prior(j) after `dep`: every per-column input is tied to the previous
-        // column's D by an empty asm, so the columns run in order.  Left free,
+        // column's E by an empty asm, so the columns run in order.  Left free,
         // the scheduler hoists all C columns' I * xx, priors and M products to
         // the top of the step (~6 extra VGPRs per column: 256 VGPRs and spills
         // at C = 16).
@@ -506,25 +551,25 @@ __global__ __launch_bounds__(64, 2) void phmm4_kernel(
           return pf2{sel_v((uint32_t)a, e1.x, e3.x), sel_v((uint32_t)c, e1.y, e3.y)};
         };
         pf2 Mn = xcur * prior(0, xcur);
-        pf2 D = din, Mp = pf2{0.f, 0.f}, Dp = pf2{0.f, 0.f};
+        pf2 E = din, Mp = pf2{0.f, 0.f}, Ep = pf2{0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < C; ++j) {
           const pf2 M = Mn;
-          if (j > 0) D = __builtin_elementwise_fma(Mp, my, Dp * yy);
+          if (j > 0) E = __builtin_elementwise_fma(Ep, yy, Mp);
           pf2 I = In[j], Xo = Xn[j];
-          asm volatile("" : "+v"(I), "+v"(Xo) : "v"(D));
-          if (j + 1 < C) Mn = Xo * prior(j + 1, D);
-          pf2 xn = __builtin_elementwise_fma(M, mm, __builtin_elementwise_fma(I, gm, D));
+          asm volatile("" : "+v"(I), "+v"(Xo) : "v"(E));
+          if (j + 1 < C) Mn = Xo * prior(j + 1, E);
+          pf2 xn = __builtin_elementwise_fma(E, cb, __builtin_elementwise_fma(I, ca, M));
           pf2 in = __builtin_elementwise_fma(M, mx, I * xx);
           asm volatile("" : "+v"(xn), "+v"(in));  // and its outputs leave it in order
           Xn[j] = xn;
           In[j] = in;
           Mp = M;
-          Dp = D;
+          Ep = E;
         }
-        dn = __builtin_elementwise_fma(Mp, my, Dp * yy);
+        dn = __builtin_elementwise_fma(Ep, yy, Mp);
         xo = Xn[C - 1];
-        // lane 15's D entering column 16 C + 1, kept per step in LDS (EXEC
+        // lane 15's E entering column 16 C + 1, kept per step in LDS (EXEC
         // narrowed to the lanes 15 inside the statement, no branch): at a V row
         // it is the half's sum, taken after the block
         uint64_t keep;
@@ -543,7 +588,7 @@ __global__ __launch_bounds__(64, 2) void phmm4_kernel(
         (step(std::integral_constant<int, S>{}), ...);
       }(std::make_integer_sequence<int, 8>{});
       if (any_cap) {
-        // lane 15 at a V row: the D entering column 16 C + 1 is the half's sum
+        // lane 15 at a V row: the E entering column 16 C + 1 is the half's sum
 #pragma unroll
         for (int h = 0; h < 2; ++h)
           if (sl == 15 && (unsigned)(cap[h] - g0) < 8u) {
@@ -577,15 +622,18 @@ __global__ __launch_bounds__(64, 2) void phmm4_kernel(
 // segment table hold pairs (K <= 16), and a block is 16 steps (one ring item
 // per lane and block) run as two passes over the 8-step unrolled body.
 // LDS per wave: a 48-row ring per segment (rows t0 - 15 .. t0 + 31 live at
-// once) of five 8-byte chunks per row: {e1, e3}, {my, yy}, {mm, gm}, {mx, xx},
+// once) of five 8-byte chunks per row: {e1, e3}, {b, yy}, {a, -}, {mx, xx},
 // {Tlo, Thi} with the Z flag in Thi's byte 3 (no column code selects it: codes
-// end at 6); chunk-major, then segment, then slot, so a segment's 16 lanes
+// end at 6); `a` is read alone (ds_read_b32, 8 bytes apart per lane: 0.29
+// bank-conflict cycles per LDS cycle, where the 8-byte reads have none;
+// reading the whole chunk, or moving the Z flag into it, spilled in phmm5 at
+// C = 19: DESIGN §4.1i); chunk-major, then segment, then slot, so a segment's 16 lanes
 // read 128 contiguous bytes (up to the wrap).  7,680 B ring + 256 B capture +
 // 1,536 B tables = 9,472 B: 16 waves fit the CU's 160 KB.
 constexpr int kCols1Ring = 48;
 constexpr int kCols1Chunks = 5;
 constexpr int kCols1ChunkBytes = kCols1Ring * 4 * 8;
-constexpr int kCols1CapOff = kCols1Chunks * kCols1ChunkBytes;  // lane 15's D per step of a block (4 x 16 floats)
+constexpr int kCols1CapOff = kCols1Chunks * kCols1ChunkBytes;  // lane 15's E per step of a block (4 x 16 floats)
 constexpr int kCols1TabOff = kCols1CapOff + 4 * 16 * 4;
 constexpr int kCols1Lds = kCols1TabOff + 3 * 128 * 4;
 constexpr int kCols1MaxK = 16;  // pairs per stream: one per lane of the segment table
@@ -600,8 +648,8 @@ typedef uint32_t pu2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void cols1_put(unsigned char* smem, int slot, int seg, const ColsItem& c) {
   unsigned char* const p = smem + (seg * kCols1Ring + slot) * 8;
   *reinterpret_cast<pf2*>(p) = pf2{c.e1, c.e3};
-  *reinterpret_cast<pf2*>(p + kCols1ChunkBytes) = pf2{c.my, c.yy};
-  *reinterpret_cast<pf2*>(p + 2 * kCols1ChunkBytes) = pf2{c.mm, c.gm};
+  *reinterpret_cast<pf2*>(p + kCols1ChunkBytes) = pf2{c.b, c.yy};
+  *reinterpret_cast<pf2*>(p + 2 * kCols1ChunkBytes) = pf2{c.a, 0.f};
   *reinterpret_cast<pf2*>(p + 3 * kCols1ChunkBytes) = pf2{c.mx, c.xx};
   *reinterpret_cast<pu2*>(p + 4 * kCols1ChunkBytes) = pu2{c.tlo, c.thi | (c.z != 0.f ? 0x01000000u : 0u)};
 }
@@ -792,7 +840,7 @@ __device__ __forceinline__ void cols1_stream(const PhmmDevBatch& b, const PhmmTa
   // Haplotype codes: cur (in use), nxt (the stream's next pair, taken by lane
   // l at stream row swr, i.e. step swr + l; kNever: every lane has taken it),
   // nk = the pair held in nxt.  other: bit Feed::bit(k) = pair k has a
-  // haplotype byte outside A/C/G/T/N.
+  // haplotype byte outside A/C/G/T/N, or a read row under kColsMinMm (stage B).
   uint32_t cur[NW], nxt[NW];
   int nk = -1, swr = kNever;
   unsigned other = 0u;
@@ -823,7 +871,7 @@ __device__ __forceinline__ void cols1_stream(const PhmmDevBatch& b, const PhmmTa
   // The ring's items (row base + sl per lane) in two stages one block apart.
   int kp = 0;  // stage A's cursor: the pair holding this lane's item row
   RawRow praw{-1, 0, 0, 0, 0, 0, 0};
-  int prole = 0;  // role | first << 4
+  int prole = 0;  // role | first << 4 | the row's own insertion quality << 8
   float pih = 0.f;
   bool kok = false, nok = false;
   int kG = 0, kR = 0, nG = 0;
@@ -852,10 +900,20 @@ __device__ __forceinline__ void cols1_stream(const PhmmDevBatch& b, const PhmmTa
     pih = kI;
     prole = role | (r == 0 ? 16 : 0);
     praw = (role == 2 || role == 3) ? load_raw(b, kR, kro, r) : RawRow{-1, 0, 0, 0, 0, 0, 0};
+    if (role == 2 || role == 3) prole |= (int)b.iq[kro + r] << 8;
   };
+  // kp is still the cursor stage A left for this item: a hazard row sets its
+  // pair's bit of `other` in every lane of the segment (rare: one branch).
   auto stage_b = [&](int base) {  // base >= 0
+    bool hz;
     cols1_put(smem_raw, (int)((unsigned)(base + sl) % (unsigned)kCols1Ring), seg,
-              cols_item(tab, praw, prole & 15, (prole & 16) != 0, pih));
+              cols_item(tab, praw, prole >> 8, prole & 15, (prole & 16) != 0, pih, hz));
+    if (__ballot(hz) != 0ull) {  // uniform
+      unsigned m = hz ? 1u << Feed::bit(kp) : 0u;
+#pragma unroll
+      for (int d = 1; d < 16; d <<= 1) m |= (unsigned)__shfl_xor((int)m, d, 16);
+      other |= m;
+    }
   };
   // The streams' first pairs start at row 0: a queue's come with the answer
   // to the wave's first request, a batch's are in the table and their codes
@@ -870,7 +928,8 @@ __device__ __forceinline__ void cols1_stream(const PhmmDevBatch& b, const PhmmTa
   load_cursor();
   load_cap();
   {  // ring prologue: rows -16..-1 are Z (slots 32..47), rows 0..15 built, rows 16..31 requested
-    cols1_put(smem_raw, 32 + sl, seg, cols_item(tab, RawRow{-1, 0, 0, 0, 0, 0, 0}, 0, false, 0.f));
+    bool hz;
+    cols1_put(smem_raw, 32 + sl, seg, cols_item(tab, RawRow{-1, 0, 0, 0, 0, 0, 0}, 0, 0, false, 0.f, hz));
     stage_a(0);
     stage_b(0);
     stage_a(16);
@@ -976,43 +1035,44 @@ __device__ __forceinline__ void cols1_stream(const PhmmDevBatch& b, const PhmmTa
         auto ld2 = [&](int chunk) {
           return *reinterpret_cast<const __attribute__((address_space(3))) pf2*>((uintptr_t)(pa + chunk * kCols1ChunkBytes));
         };
-        const pf2 r0 = ld2(0), r1 = ld2(1), r2 = ld2(2), r3 = ld2(3);
+        const pf2 r0 = ld2(0), r1 = ld2(1), r3 = ld2(3);
+        const float ca = *reinterpret_cast<const __attribute__((address_space(3))) float*>((uintptr_t)(pa + 2 * kCols1ChunkBytes));
         const pu2 cr = *reinterpret_cast<const __attribute__((address_space(3))) pu2*>((uintptr_t)(pa + 4 * kCols1ChunkBytes));
-        const float e1 = r0.x, e3 = r0.y, my = r1.x, yy = r1.y, mm = r2.x, gm = r2.y, mx = r3.x, xx = r3.y;
+        const float e1 = r0.x, e3 = r0.y, cb = r1.x, yy = r1.y, mx = r3.x, xx = r3.y;
         const float z = (float)(cr.y >> 24);  // v_cvt_f32_ubyte3: 1 on Z rows
-        // the lane below's D into column l*C + 1 (lane 0: 1 on Z rows, else
-        // 0) and its X(g, l*C) for the next row (lane 0: X(g, 0) = 1 after a Z row)
+        // the lane below's E into column l*C + 1 (lane 0: 1 on Z rows, else
+        // 0) and its X~(g, l*C) for the next row (lane 0: X~(g, 0) = 1 after a Z row)
         const float din = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(z), __float_as_int(dn), kDppRowShr1, 0xF, 0xF, false));
         const float xnx = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(z), __float_as_int(xo), kDppRowShr1, 0xF, 0xF, false));
         const float xcur = xin;
         xin = xnx;
         uint32_t mA = 0;
-        auto prior = [&](int j, const float dep) {  // tied to the previous column's D, as in phmm4
+        auto prior = [&](int j, const float dep) {  // tied to the previous column's E, as in phmm4
           if ((j & 3) == 0) mA = __builtin_amdgcn_perm(cr.y, cr.x, cur[j >> 2]);
           int a;
           asm volatile("v_bfe_i32 %0, %1, %2, 1" : "=v"(a) : "v"(mA), "i"(8 * (j & 3)), "v"(dep));
           return sel_v((uint32_t)a, e1, e3);
         };
         float Mn = xcur * prior(0, xcur);
-        float D = din, Mp = 0.f, Dp = 0.f;
+        float E = din, Mp = 0.f, Ep = 0.f;
 #pragma unroll
         for (int j = 0; j < C; ++j) {
           const float M = Mn;
-          if (j > 0) D = __builtin_fmaf(Mp, my, Dp * yy);
+          if (j > 0) E = __builtin_fmaf(Ep, yy, Mp);
           float I = In[j], Xo = Xn[j];
-          asm volatile("" : "+v"(I), "+v"(Xo) : "v"(D));
-          if (j + 1 < C) Mn = Xo * prior(j + 1, D);
-          float xn = __builtin_fmaf(M, mm, __builtin_fmaf(I, gm, D));
+          asm volatile("" : "+v"(I), "+v"(Xo) : "v"(E));
+          if (j + 1 < C) Mn = Xo * prior(j + 1, E);
+          float xn = __builtin_fmaf(E, cb, __builtin_fmaf(I, ca, M));
           float in = __builtin_fmaf(M, mx, I * xx);
           asm volatile("" : "+v"(xn), "+v"(in));
           Xn[j] = xn;
           In[j] = in;
           Mp = M;
-          Dp = D;
+          Ep = E;
         }
-        dn = __builtin_fmaf(Mp, my, Dp * yy);
+        dn = __builtin_fmaf(Ep, yy, Mp);
         xo = Xn[C - 1];
-        // lane 15's D entering column 16 C + 1, kept per step in LDS: at a V
+        // lane 15's E entering column 16 C + 1, kept per step in LDS: at a V
         // row it is the stream's sum, taken after the block
         uint64_t keep;
         const uint32_t cpa = capa + 0u;
@@ -1036,7 +1096,7 @@ __device__ __forceinline__ void cols1_stream(const PhmmDevBatch& b, const PhmmTa
       xs = min(xs, xs - (uint32_t)(kCols1Ring * 8));
     }
     if (any_cap) {
-      // lane 15 at a V row: the D entering column 16 C + 1 is the stream's sum
+      // lane 15 at a V row: the E entering column 16 C + 1 is the stream's sum
       if (sl == 15 && (unsigned)(cap - gb) < 16u) {
         const float acc = *reinterpret_cast<const float*>(smem_raw + kCols1CapOff + seg * 64 + 4 * (cap - gb));
         const int p = capp;
