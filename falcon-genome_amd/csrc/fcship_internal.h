@@ -42,6 +42,19 @@ struct DeviceScope {
   ::fcs::DeviceScope _fcs_device_scope;   \
   FCS_HIP_CHECK(hipSetDevice(d))
 
+// ------------------------------------------------------------ arena planner
+inline size_t pad256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// Places arrays one after another at multiples of 256 bytes.
+struct Arena {
+  size_t total = 0;
+  size_t add(size_t bytes) {
+    const size_t o = total;
+    total += pad256(bytes);
+    return o;
+  }
+};
+
 // ------------------------------------------------------------ DPP cross-lane
 // CDNA (gfx9) DPP controls.  row = 16 lanes.
 enum : int {
@@ -315,7 +328,7 @@ int launch_fmd_seed(const FmdDevIndex& dx, const FmdIv* slots, int32_t max_mems,
                     int64_t* rows, int64_t* pos, int64_t row_cap, hipStream_t s);
 
 // ------------------------------------------------------------ call sessions
-// A pooled compute session (fcship_api.cpp) leased for one synchronous call of
+// A pooled compute session (session.cpp) leased for one synchronous call of
 // an entry point that lives in another file (markdup.hip): its stream and its
 // pinned host and device arenas, grown to the sizes asked for.  The release
 // synchronises the stream before the session goes back to the pool.

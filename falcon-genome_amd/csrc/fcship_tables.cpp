@@ -1,5 +1,5 @@
 // Host construction of the GKL PairHMM constant tables (Context<float> /
-// Context<double>), uploaded once per device by fcship_api.cpp.
+// Context<double>), uploaded once per device by session.cpp.
 //
 // These are part of the algorithm, not a check: the kernels read them instead
 // of evaluating powf/log on the device so that every table entry is the value

@@ -2,8 +2,8 @@
 // share around their kernels.  A batch is n records over flat arrays: a CIGAR
 // word range and a base range per record, by two arrays of n + 1 offsets.
 //
-// Host side: the arena planner, the offset and scalar checks of the entry
-// points, and the layout-and-stage pair of fcsdp_batch, fcsug_batch and
+// Host side: the offset and scalar checks of the entry points, and the
+// layout-and-stage pair (over fcship_internal.h's Arena) of fcsdp_batch, fcsug_batch and
 // fcsbq_batch (the same field names).  A staged batch holds only the CIGAR
 // words and bases [off[0], off[n]) and keeps the caller's offsets: the device
 // view's cigar / bases / qual pointers are shifted down by the first offsets.
@@ -21,18 +21,6 @@
 #include "fcship_internal.h"
 
 namespace fcs {
-
-inline size_t pad256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// Places arrays one after another at multiples of 256 bytes.
-struct Arena {
-  size_t total = 0;
-  size_t add(size_t bytes) {
-    const size_t o = total;
-    total += pad256(bytes);
-    return o;
-  }
-};
 
 // The n + 1 offsets of the `what` ranges into `total` elements; with max_len
 // also that no record's range is longer.

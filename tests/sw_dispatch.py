@@ -59,7 +59,7 @@ ALIGN_MATS = {
 
 # ------------------------------------------------------------------ restated predicates
 def to_params(mat, o_del=6, e_del=1, o_ins=6, e_ins=1, end_bonus=5, zdrop=100):
-    """csrc/fcship_api.cpp to_params: the derived fields."""
+    """csrc/bsw_api.cpp to_params: the derived fields."""
     m = [int(v) for v in np.asarray(mat).ravel()]
     assert len(m) == 25
     p = SimpleNamespace(mat=m, o_del=o_del, e_del=e_del, o_ins=o_ins, e_ins=e_ins, end_bonus=end_bonus, zdrop=zdrop)

@@ -530,3 +530,100 @@ def test_global_lane_kernel_32bit_form(gpu, shape):
         assert np.array_equal(cigars[k], rc), f"task {k}: {fcship.cigar_str(cigars[k])} != {fcship.cigar_str(rc)}"
     s2, _ = fcship.bsw_global(t, params, with_cigar=False)
     assert np.array_equal(s2, scores)
+
+
+def staging_tasks():
+    """The smallest batch at which the host calls' staging can go wrong: an
+    empty target, a one-base query and a plain task, so that the byte buffers,
+    the per-task arrays and each call's outputs all have different sizes."""
+    rng = np.random.default_rng(1801)
+    q0, _ = related_pair(rng, 40, 40)
+    q2, t2 = related_pair(rng, 70, 66, sub=0.05, indel=0.02)
+    return fcship.make_tasks([(q0, np.zeros(0, np.uint8), 7, 12), (np.array([2], np.uint8), t2[:30].copy(), 3, 5),
+                              (q2, t2, 20, 15)])
+
+
+def test_host_calls_stage_three_uneven_tasks(gpu):
+    """fcs_bsw_extend_batch, fcs_bsw_extend, fcs_bsw_global and fcs_bsw_align on
+    staging_tasks(), each bit-exact against the oracle.  The global call's
+    CIGAR slots leave a gap after every slot, so the arena size, the direction
+    matrix size and the span copied back all differ."""
+    t = staging_tasks()
+    m = fcship.default_mat()
+    ref, rcells = oracle_lib.ksw_extend2_batch(t, m)
+    res, cells = fcship.bsw_extend_batch(t)
+    assert np.array_equal(res, ref) and np.array_equal(cells, rcells)
+    assert np.array_equal(fcship.bsw_extend_tasks(t), ref)
+    n = t.n
+    tasks = (fcship.BswTask * n)()
+    for k in range(n):
+        q, tg, _, w = t.task(k)
+        tasks[k] = fcship.BswTask(len(q), len(tg), 1, w, q.ctypes.data_as(fcship.u8p) if q.size else None,
+                                  tg.ctypes.data_as(fcship.u8p) if tg.size else None)
+    cap = (t.qlen + t.tlen + 2).astype(np.int32)
+    off = np.concatenate([[0], np.cumsum(cap.astype(np.int64) + 5)[:-1]]).astype(np.int64)  # five spare words a slot
+    arena = np.zeros(int(off[-1] + cap[-1]), np.uint32)
+    scores, ncig = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    params = fcship.bsw_params()
+    fcship.check(fcship.lib.fcs_bsw_global(tasks, n, fcship.C.byref(params), scores.ctypes.data_as(fcship.i32p),
+                                           arena.ctypes.data_as(fcship.u32p), off.ctypes.data_as(fcship.i64p),
+                                           cap.ctypes.data_as(fcship.i32p), ncig.ctypes.data_as(fcship.i32p), gpu))
+    for k in range(n):
+        q, tg, _, w = t.task(k)
+        rs, rc = oracle_lib.ksw_global2(q, tg, w, m)
+        got = arena[off[k]:off[k] + ncig[k]]
+        assert scores[k] == rs and np.array_equal(got, rc), f"task {k}: {scores[k]} {fcship.cigar_str(got)}"
+    s2, _ = fcship.bsw_global(t, with_cigar=False)
+    assert np.array_equal(s2, scores)
+    for x in (fcship.KSW_XSTART | fcship.KSW_XBYTE, fcship.KSW_XSTART):
+        got = fcship.bsw_align(t, x)
+        for k in range(n):
+            q, tg, _, _ = t.task(k)
+            assert tuple(got[k]) == oracle_lib.ksw_align2(q, tg, m, x), (hex(x), k)
+
+
+def test_extend_plan_and_align_dev_on_device_batches(gpu):
+    """fcs_bsw_extend_plan (a caller's plan, one task more than the batch and
+    exactly the batch) and fcs_bsw_align_dev over device arrays on the
+    caller's stream: bit-exact against the oracle, as the host calls are."""
+    import torch
+    dev = torch.device("cuda", gpu)
+    m = fcship.default_mat()
+    params = fcship.bsw_params()
+    s = torch.cuda.current_stream(dev)
+
+    def on_device(t):
+        keep = {n: torch.from_numpy(np.ascontiguousarray(getattr(t, n))).to(dev)
+                for n in ("qbuf", "qoff", "qlen", "tbuf", "toff", "tlen", "h0", "w")}
+        b = t.to_struct()
+        for n, x in keep.items():
+            setattr(b, n, x.data_ptr())
+        return b, keep
+
+    t = random_tasks(1802, 300)
+    ref, rcells = oracle_lib.ksw_extend2_batch(t, m)
+    b, keep = on_device(t)
+    for cap in (t.n + 1, t.n):
+        plan = fcship.C.c_void_p()
+        fcship.check(fcship.lib.fcs_bsw_plan_create(gpu, cap, fcship.C.byref(plan)))
+        try:
+            res = torch.zeros((t.n, 6), dtype=torch.int32, device=dev)
+            cells = torch.zeros(t.n, dtype=torch.int64, device=dev)
+            fcship.check(fcship.lib.fcs_bsw_extend_plan(plan, fcship.C.byref(b), fcship.C.byref(params), res.data_ptr(),
+                                                        cells.data_ptr(), s.cuda_stream))
+            torch.cuda.synchronize(dev)
+            assert np.array_equal(res.cpu().numpy(), ref) and np.array_equal(cells.cpu().numpy(), rcells)
+        finally:
+            fcship.check(fcship.lib.fcs_bsw_plan_destroy(plan))
+    t = align_tasks(1803, 90)
+    b, keep = on_device(t)
+    xs = np.array([fcship.KSW_XSTART | (fcship.KSW_XBYTE if k % 3 else 0) for k in range(t.n)], np.int32)
+    d_x = torch.from_numpy(xs).to(dev)
+    out = torch.zeros((t.n, 7), dtype=torch.int32, device=dev)
+    fcship.check(fcship.lib.fcs_bsw_align_dev(fcship.C.byref(b), fcship.C.byref(params), d_x.data_ptr(), out.data_ptr(),
+                                              gpu, s.cuda_stream))
+    torch.cuda.synchronize(dev)
+    got = out.cpu().numpy()
+    for k in range(t.n):
+        q, tg, _, _ = t.task(k)
+        assert tuple(got[k]) == oracle_lib.ksw_align2(q, tg, m, int(xs[k])), (k, len(q), len(tg))

@@ -199,6 +199,44 @@ def test_capacity_through_the_binding(gpu, host_plain, index8):
     assert_flat(got, want)
 
 
+def test_three_reads_a_tie_and_both_end_bins(gpu, host_plain, index8):
+    """The smallest batch at which the read staging of fcs_fmd_seed and
+    fcs_fmd_collect can go wrong: a zero-length read between two of equal
+    length, so the longest-first counting sort has a tie in its first bin and
+    fills its last.  Capacities one short of the totals give FCS_FMD_SEED_MORE
+    with nothing written; the totals give the host's content; collect returns
+    the host's SMEMs read by read."""
+    h, sa1 = index8
+    reads = S.plain_batch()
+    by_len = {}
+    for i, q in enumerate(reads):
+        if len(host_plain[S.BWA][0][i]):
+            by_len.setdefault(len(q), []).append(i)
+    a, b = next(v for v in by_len.values() if len(v) >= 2)[:2]
+    batch = [reads[a], "", reads[b]]
+    host_mems = [host_plain[S.BWA][0][a], np.zeros((0, 5), np.int64), host_plain[S.BWA][0][b]]
+    want = flat(host_mems, sa1)
+    tm, tr = int(want[1][-1]), int(want[3][-1])
+    assert tm >= 2 and tr >= tm
+    for mem_cap, row_cap in ((tm - 1, tr), (tm, tr - 1)):
+        mems = np.zeros(tm, fcship.FMD_MEM)
+        mems.view(np.uint8)[:] = 0x5A
+        pos = np.full(tr, -77, np.int64)
+        got = fcship.fmd_seed(h, *S.soa(batch), mem_cap=mem_cap, row_cap=row_cap, mems=mems, pos=pos)
+        assert got[5] == fcship.FCS_FMD_SEED_MORE
+        assert np.array_equal(got[1], want[1]) and np.array_equal(got[3], want[3]) and not got[4].any()
+        assert (mems.view(np.uint8) == 0x5A).all() and (pos == -77).all()
+    got = fcship.fmd_seed(h, *S.soa(batch), mem_cap=tm, row_cap=tr)
+    assert got[5] == fcship.FCS_OK and not got[4].any()
+    assert_flat(got, want)
+    assert got[1][1] == got[1][2] and got[3][1] == got[3][2]
+    mems, n_mems, overflow = fcship.fmd_collect(h, *S.soa(batch))
+    assert not overflow.any() and list(n_mems) == [len(m) for m in host_mems]
+    for r in range(3):
+        m = mems[r, :n_mems[r]]
+        assert np.array_equal(np.stack([m["qb"], m["qe"], m["s"], m["k"], m["l"]], 1).reshape(-1, 5), host_mems[r])
+
+
 def test_empty_batch(gpu, index8):
     h, _ = index8
     e = np.zeros(0, np.uint8), np.zeros(0, np.int64), np.zeros(0, np.int32)
