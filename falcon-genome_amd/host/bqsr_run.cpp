@@ -7,15 +7,13 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
-#include <sstream>
 #include <unordered_map>
 
-#include "bam.h"
+#include "bam_stream.h"
 #include "bgzf.h"
 #include "bqsr.h"
 #include "common.h"
 #include "config.h"
-#include "fasta.h"
 #include "fcship.h"
 #include "flat_batch.h"
 #include "intervals.h"
@@ -29,7 +27,6 @@ struct BqApi {
   decltype(&fcsbq_ref_destroy) ref_destroy = FCSG_DEVICE_ENTRY(fcsbq_ref_destroy);
   decltype(&fcsbq_count) count = FCSG_DEVICE_ENTRY(fcsbq_count);
   decltype(&fcsbq_apply) apply = FCSG_DEVICE_ENTRY(fcsbq_apply);
-  LastErrorFn last_error = last_error_entry();
 };
 
 const BqApi& bq_api() {
@@ -44,31 +41,10 @@ int device_of(const BqsrJob& job) {
                         "qualities are recalibrated on the host\n");
 }
 
-// The input's BAM files: the file itself, or a directory's part BAMs in name order.
-std::vector<std::string> input_bams(const std::string& input) {
-  if (is_regular_file(input)) return {input};
-  if (!is_directory(input)) throw fileNotFound(input);
-  std::vector<std::string> names = list_dir(input, ".bam");
-  std::sort(names.begin(), names.end());
-  std::vector<std::string> out;
-  for (const std::string& n : names) out.push_back(n.find('/') == std::string::npos ? input + "/" + n : n);
-  if (out.empty()) throw fileNotFound(input + "/*.bam");
-  return out;
-}
-
 // The header's read groups: ids[k] the @RG ID, names[k] its PU when present, else the ID.
 void read_groups(const BamHeader& h, std::vector<std::string>& ids, std::vector<std::string>& names) {
-  std::istringstream ss(h.text);
-  for (std::string line; std::getline(ss, line);) {
-    if (line.rfind("@RG", 0) != 0) continue;
-    std::string id, pu;
-    for (size_t p = 0; p < line.size();) {
-      const size_t e = std::min(line.find('\t', p), line.size());
-      const std::string f = line.substr(p, e - p);
-      if (f.rfind("ID:", 0) == 0) id = f.substr(3);
-      if (f.rfind("PU:", 0) == 0) pu = f.substr(3);
-      p = e + 1;
-    }
+  for (const RgLine& rg : rg_lines(h)) {
+    const std::string id = rg.get("ID"), pu = rg.get("PU");
     if (id.empty()) continue;
     ids.push_back(id);
     names.push_back(pu.empty() ? id : pu);
@@ -88,13 +64,9 @@ struct BqGenome {
 };
 
 BqGenome load_genome(const std::string& fasta, const BamHeader& h) {
-  const Reference ref = load_fasta(fasta);
   BqGenome g;
   g.ref_off.assign(1, 0);
-  for (size_t k = 0; k < h.names.size(); ++k) {
-    const int c = ref.index(h.names[k]);
-    if (c < 0) throw invalidParam("contig " + h.names[k] + " of the BAM header is not in " + fasta);
-    const std::string& s = ref.contigs[(size_t)c].seq;
+  for (const std::string& s : header_contigs(fasta, h, false)) {  // a length that differs from the header's is taken as it is
     g.bases.insert(g.bases.end(), s.begin(), s.end());
     g.ref_off.push_back((int64_t)g.bases.size());
   }
@@ -188,44 +160,32 @@ fcsbq_batch flat_view(const std::vector<BamRecord>& recs, const std::vector<int3
 // The job's input, read chunk by chunk: the records -L keeps, with their read group indices.
 class ChunkReader {
  public:
-  ChunkReader(const BqsrJob& job) : bams_(input_bams(job.input)) {
-    reader_.reset(new BamReader(bams_[0]));
-    header_ = reader_->header();
-    read_groups(header_, ids_, names_);
-    for (size_t k = 0; k < ids_.size(); ++k) rg_index_.emplace(ids_[k], (int32_t)k);
-    regions_ = load_regions(job.intervals, header_);
+  ChunkReader(const BqsrJob& job) : in_(job.input, false) {
+    std::vector<std::string> ids;
+    read_groups(header(), ids, names_);
+    for (size_t k = 0; k < ids.size(); ++k) rg_index_.emplace(ids[k], (int32_t)k);
+    regions_ = load_regions(job.intervals, header());
     chunk_ = (size_t)std::max(conf().get_int("bqsr.chunk_records"), 1);
   }
-  const BamHeader& header() const { return header_; }
+  const BamHeader& header() const { return in_.header(); }
   const std::vector<std::string>& rg_names() const { return names_; }
   bool next(std::vector<BamRecord>& recs, std::vector<int32_t>& rg) {
-    recs.clear(), rg.clear();
-    BamRecord r;
+    recs.clear();
+    in_.read(recs, chunk_, [&](const BamRecord& r) { return regions_.keep(r); });
+    rg.assign(recs.size(), -1);
     std::string id;
-    while (recs.size() < chunk_) {
-      if (!reader_->next(r)) {
-        if (++file_ >= bams_.size()) break;
-        reader_.reset(new BamReader(bams_[file_]));
-        continue;
-      }
-      if (!regions_.keep(r)) continue;
-      int32_t g = -1;
-      if (r.get_aux_string("RG", id)) {
+    for (size_t k = 0; k < recs.size(); ++k)
+      if (recs[k].get_aux_string("RG", id)) {
         const auto it = rg_index_.find(id);
-        if (it != rg_index_.end()) g = it->second;
+        if (it != rg_index_.end()) rg[k] = it->second;
       }
-      rg.push_back(g);
-      recs.push_back(std::move(r));
-    }
     return !recs.empty();
   }
 
  private:
-  std::vector<std::string> bams_;
-  std::unique_ptr<BamReader> reader_;
-  size_t file_ = 0, chunk_ = 1;
-  BamHeader header_;
-  std::vector<std::string> ids_, names_;
+  BamStream in_;
+  size_t chunk_ = 1;
+  std::vector<std::string> names_;
   std::unordered_map<std::string, int32_t> rg_index_;
   Regions regions_;
 };
@@ -235,8 +195,8 @@ struct DeviceRef {
   fcsbq_ref* h = nullptr;
   DeviceRef(int device, const BqGenome& g) {
     if (device < 0) return;
-    if (bq_api().ref_create(device, g.bases.data(), g.ref_off.data(), (int32_t)g.ref_off.size() - 1, g.known.data(), &h) != FCS_OK)
-      throw failedCommand(std::string("[E::fcs-genome bqsr] fcsbq_ref_create: ") + bq_api().last_error());
+    device_check(bq_api().ref_create(device, g.bases.data(), g.ref_off.data(), (int32_t)g.ref_off.size() - 1, g.known.data(), &h),
+                 "bqsr", "fcsbq_ref_create");
   }
   ~DeviceRef() {
     if (h) bq_api().ref_destroy(h);
@@ -276,12 +236,8 @@ void count_pass(const BqsrJob& job, int device, CountTables& t, std::vector<std:
     for (int64_t r = 0; r < b.n; ++r)
       st.counted += b.rg[r] >= 0 && !b.qual_absent[r] && !(b.flag[r] & 0x704) && b.mapq[r] != 0 && b.mapq[r] != 255;
     st.records += b.n;
-    if (device >= 0) {
-      if (bq_api().count(dref.h, &b, t.n_rg, t.ctx.data(), t.cyc.data()) != FCS_OK)
-        throw failedCommand(std::string("[E::fcs-genome bqsr] fcsbq_count: ") + bq_api().last_error());
-    } else {
-      bqsr_count_host(g.view(), b, t.n_rg, t.ctx.data(), t.cyc.data(), host_threads());
-    }
+    if (device >= 0) device_check(bq_api().count(dref.h, &b, t.n_rg, t.ctx.data(), t.cyc.data()), "bqsr", "fcsbq_count");
+    else bqsr_count_host(g.view(), b, t.n_rg, t.ctx.data(), t.cyc.data(), host_threads());
   }
   sum_tables(t, st);
 }
@@ -305,8 +261,8 @@ void apply_pass(const BqsrJob& job, int device, const BqTables& tables, BqsrStat
     const fcsbq_batch b = flat_view(recs, rg, order, f, flat_rg);
     out.assign((size_t)b.n_bases + 1, 0);
     if (device >= 0) {
-      if (bq_api().apply(device, &b, tables.n_rg, tables.base.data(), tables.dctx.data(), tables.dcyc.data(), out.data()) != FCS_OK)
-        throw failedCommand(std::string("[E::fcs-genome bqsr] fcsbq_apply: ") + bq_api().last_error());
+      device_check(bq_api().apply(device, &b, tables.n_rg, tables.base.data(), tables.dctx.data(), tables.dcyc.data(), out.data()),
+                   "bqsr", "fcsbq_apply");
     } else {
       bqsr_apply_host(b, tables, out.data(), host_threads());
     }
@@ -323,7 +279,7 @@ void apply_pass(const BqsrJob& job, int device, const BqTables& tables, BqsrStat
 }
 
 std::vector<std::string> header_rg_names(const BqsrJob& job) {
-  BamReader in(input_bams(job.input)[0]);
+  BamReader in(bam_inputs(job.input)[0]);
   std::vector<std::string> ids, names;
   read_groups(in.header(), ids, names);
   return names;
@@ -333,7 +289,7 @@ std::vector<std::string> header_rg_names(const BqsrJob& job) {
 
 bool gpu_bqsr_available() {
   const BqApi& a = bq_api();
-  return a.ref_create && a.ref_destroy && a.count && a.apply && a.last_error;
+  return a.ref_create && a.ref_destroy && a.count && a.apply && last_error_entry();
 }
 
 BqsrStats baserecal_run(const BqsrJob& job) {

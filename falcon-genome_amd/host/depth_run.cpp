@@ -6,23 +6,17 @@
 #include "depth_run.h"
 
 #include <algorithm>
-#include <climits>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <map>
-#include <memory>
-#include <set>
-#include <sstream>
 
-#include "bam.h"
+#include "bam_stream.h"
 #include "common.h"
 #include "config.h"
 #include "depth.h"
-#include "fasta.h"
 #include "fcship.h"
 #include "flat_batch.h"
-#include "intervals.h"
 
 namespace fcsg {
 
@@ -31,23 +25,12 @@ namespace {
 struct DpApi {
   decltype(&fcsdp_count) count = FCSG_DEVICE_ENTRY(fcsdp_count);
   decltype(&fcsdp_stats) stats = FCSG_DEVICE_ENTRY(fcsdp_stats);
-  LastErrorFn last_error = last_error_entry();
 };
 
 const DpApi& dp_api() {
   static const DpApi A;
   return A;
 }
-
-struct Part {
-  size_t interval;
-  int64_t start, end;  // window offsets
-};
-
-struct Window {
-  fcsdp_window w;
-  std::vector<Part> parts;
-};
 
 // max_end[k]: the running maximum of the ends of records [.., k] on their contig.
 void running_max_end(const std::vector<BamRecord>& recs, std::vector<int64_t>& max_end) {
@@ -58,9 +41,6 @@ void running_max_end(const std::vector<BamRecord>& recs, std::vector<int64_t>& m
   }
 }
 
-// The sort key of a record: unmapped records without a contig come last.
-std::pair<int64_t, int64_t> key_of(int32_t ref_id, int32_t pos) { return {ref_id < 0 ? (int64_t)INT32_MAX + 1 : ref_id, pos}; }
-
 class Run {
  public:
   explicit Run(const DepthJob& job)
@@ -68,20 +48,10 @@ class Run {
         device_(device_or_host(job.device, gpu_depth_available(),
                                "[fcs-genome depth] depth.gpu: the loaded libfcship has no fcsdp_count entry point; "
                                "depths are counted on the host\n")),
-        bams_(sorted_bam_inputs(job.input)) {
-    reader_.reset(new BamReader(bams_[0]));
-    header_ = reader_->header();
+        in_(job.input, true),
+        header_(in_.header()) {
     st_.sample = single_sample(header_, "depth");
-    const Reference ref = load_fasta(job.ref);
-    contigs_.resize(header_.names.size());
-    for (size_t k = 0; k < header_.names.size(); ++k) {
-      const int c = ref.index(header_.names[k]);
-      if (c < 0) throw invalidParam("contig " + header_.names[k] + " of the BAM header is not in " + job.ref);
-      contigs_[k] = ref.contigs[(size_t)c].seq;
-      if ((int64_t)contigs_[k].size() != header_.lengths[k])
-        throw invalidParam("contig " + header_.names[k] + " has " + std::to_string(header_.lengths[k]) +
-                           " bases in the BAM header and " + std::to_string(contigs_[k].size()) + " in " + job.ref);
-    }
+    contigs_ = header_contigs(job.ref, header_, true);
     Config& cf = conf();
     prm_.min_mapq = cf.get_int("depth.min_mapq"), prm_.max_mapq = cf.get_int("depth.max_mapq");
     prm_.min_baseq = cf.get_int("depth.min_baseq"), prm_.max_baseq = cf.get_int("depth.max_baseq");
@@ -90,9 +60,10 @@ class Run {
       throw invalidParam("depth.min_mapq / max_mapq or depth.min_baseq / max_baseq: a lower bound above its upper bound");
     include_ref_n_ = cf.get_bool("depth.include_ref_n");
     chunk_ = (size_t)std::max(cf.get_int("depth.chunk_records"), 1);
-    window_bp_ = std::clamp<int64_t>(cf.get_int("depth.window_bp"), 1, FCSDP_WINDOW_MAX);
+    const int64_t window_bp = std::clamp<int64_t>(cf.get_int("depth.window_bp"), 1, FCSDP_WINDOW_MAX);
     intervals_ = merged_intervals(job.intervals, header_);
-    cut_windows();
+    windows_ = cut_windows(intervals_, header_.lengths, window_bp);
+    name_rows();
     hist_.assign(FCSDP_BINS, 0);
     long_hist_.assign((size_t)FCSDP_BINS * n_long_, 0);
   }
@@ -124,15 +95,15 @@ class Run {
     std::vector<BamRecord> recs;
     FlatRecords f;
     std::vector<int64_t> max_end;
-    while (next_chunk(recs)) {
+    while (recs.clear(), in_.read(recs, chunk_) > 0) {
       st_.records += (int64_t)recs.size();
       flatten(recs, recs.size(), false, f);
       running_max_end(recs, max_end);
       count_chunk(f, max_end);
       const auto last = key_of(f.ref_id.back(), f.pos.back());
-      while (cur_ < windows_.size() && (windows_[cur_].w.ref_id < last.first ||
-                                        (windows_[cur_].w.ref_id == last.first &&
-                                         windows_[cur_].w.start + windows_[cur_].w.len <= last.second)))
+      while (cur_ < windows_.size() && (windows_[cur_].ref_id < last.first ||
+                                        (windows_[cur_].ref_id == last.first &&
+                                         windows_[cur_].start + windows_[cur_].len <= last.second)))
         finish_window(cur_++);
       if (interrupted()) throw interruptedError();
     }
@@ -140,61 +111,19 @@ class Run {
     write_files();
   }
 
-  // Windows of at most window_bp loci from each contig's first interval start to its last interval end;
-  // an interval cut by a window edge or longer than a piece gets a row of long_hist.
-  void cut_windows() {
+  // The intervals' rows; an interval cut by a window edge or longer than a piece gets a row of long_hist.
+  void name_rows() {
     rows_.resize(intervals_.size());
     long_index_.assign(intervals_.size(), -1);
-    for (size_t a = 0; a < intervals_.size();) {
-      size_t b = a;
-      while (b < intervals_.size() && intervals_[b].ref == intervals_[a].ref) ++b;
-      const int32_t ref = intervals_[a].ref;
-      size_t k = a;
-      for (int64_t s = intervals_[a].start; s < intervals_[b - 1].end; s += window_bp_) {
-        Window win;
-        win.w.ref_id = ref, win.w.reserved = 0, win.w.start = s;
-        win.w.len = std::min(window_bp_, intervals_[b - 1].end - s), win.w.contig_len = header_.lengths[(size_t)ref];
-        const int64_t e = s + win.w.len;
-        while (k < b && intervals_[k].end <= s) ++k;
-        for (size_t j = k; j < b && intervals_[j].start < e; ++j)
-          win.parts.push_back({j, std::max(intervals_[j].start, s) - s, std::min(intervals_[j].end, e) - s});
-        if (!win.parts.empty()) windows_.push_back(std::move(win));
-      }
-      a = b;
-    }
     std::vector<int> n_parts(intervals_.size(), 0);
-    for (const Window& w : windows_)
-      for (const Part& p : w.parts) ++n_parts[p.interval];
+    for (const GenomeWindow& w : windows_)
+      for (const GenomeWindow::Part& p : w.parts) ++n_parts[p.interval];
     for (size_t j = 0; j < intervals_.size(); ++j) {
       const GenomeInterval& i = intervals_[j];
       if (n_parts[j] > 1 || i.end - i.start > FCSDP_PIECE_MAX) long_index_[j] = n_long_++;
       rows_[j].name = header_.names[(size_t)i.ref] + ":" + std::to_string(i.start + 1) +
                       (i.end - i.start > 1 ? "-" + std::to_string(i.end) : "");
     }
-  }
-
-  bool next_chunk(std::vector<BamRecord>& recs) {
-    recs.clear();
-    BamRecord r;
-    while (recs.size() < chunk_) {
-      if (!reader_->next(r)) {
-        if (++file_ >= bams_.size()) break;
-        reader_.reset(new BamReader(bams_[file_]));
-        continue;
-      }
-      const auto key = key_of(r.ref_id, r.pos);
-      if (key < last_key_) {
-        auto where = [&](int64_t ref, int64_t pos) {
-          return (ref >= 0 && ref < (int64_t)header_.names.size() ? header_.names[(size_t)ref] : std::string("*")) + ":" +
-                 std::to_string(pos + 1);
-        };
-        throw invalidParam("the input is not coordinate-sorted: record " + r.name + " at " + where(r.ref_id, r.pos) +
-                           " follows one at " + where(last_key_.first, last_key_.second));
-      }
-      last_key_ = key;
-      recs.push_back(std::move(r));
-    }
-    return !recs.empty();
   }
 
   // The chunk's records given to every window they overlap.
@@ -212,7 +141,7 @@ class Run {
     if (segs.empty()) return;
     size_t si = 0;
     for (size_t wi = cur_; wi < windows_.size(); ++wi) {
-      const fcsdp_window& w = windows_[wi].w;
+      const fcsdp_window w = windows_[wi].as<fcsdp_window>();
       while (si < segs.size() && segs[si].ref < w.ref_id) ++si;
       if (si == segs.size()) break;
       if (segs[si].ref > w.ref_id) continue;
@@ -227,25 +156,20 @@ class Run {
       std::vector<uint32_t>& depth = open_[wi];
       if (depth.empty()) depth.assign((size_t)w.len, 0);
       const fcsdp_batch view = f.view<fcsdp_batch>(lo, hi);
-      if (device_ >= 0) {
-        if (dp_api().count(device_, &view, &prm_, &w, depth.data()) != FCS_OK)
-          throw failedCommand(std::string("[E::fcs-genome depth] fcsdp_count: ") + dp_api().last_error());
-      } else {
-        depth_count_host(view, prm_, w, depth.data(), host_threads());
-      }
+      if (device_ >= 0) device_check(dp_api().count(device_, &view, &prm_, &w, depth.data()), "depth", "fcsdp_count");
+      else depth_count_host(view, prm_, w, depth.data(), host_threads());
     }
   }
 
   void finish_window(size_t wi) {
-    const Window& win = windows_[wi];
-    const fcsdp_window& w = win.w;
+    const GenomeWindow& w = windows_[wi];
     std::vector<uint32_t> depth = std::move(open_[wi]);
     open_.erase(wi);
     if (depth.empty()) depth.assign((size_t)w.len, 0);
     const std::string& seq = contigs_[(size_t)w.ref_id];
     std::vector<uint64_t> bitmap((size_t)(w.len + 63) / 64, 0);
     std::vector<fcsdp_piece> pieces;
-    for (const Part& p : win.parts) {
+    for (const GenomeWindow::Part& p : w.parts) {
       for (int64_t i = p.start; i < p.end; ++i) {
         const char c = seq[(size_t)(w.start + i)];
         if (include_ref_n_ || (c != 'N' && c != 'n')) bitmap[(size_t)(i >> 6)] |= (uint64_t)1 << (i & 63);
@@ -255,15 +179,15 @@ class Run {
     }
     std::vector<fcsdp_summary> sum(pieces.size());
     if (device_ >= 0) {
-      if (dp_api().stats(device_, depth.data(), bitmap.data(), w.len, pieces.data(), (int64_t)pieces.size(), (int32_t)n_long_,
-                         hist_.data(), long_hist_.data(), sum.data()) != FCS_OK)
-        throw failedCommand(std::string("[E::fcs-genome depth] fcsdp_stats: ") + dp_api().last_error());
+      device_check(dp_api().stats(device_, depth.data(), bitmap.data(), w.len, pieces.data(), (int64_t)pieces.size(),
+                                  (int32_t)n_long_, hist_.data(), long_hist_.data(), sum.data()),
+                   "depth", "fcsdp_stats");
     } else {
       depth_stats_host(depth.data(), bitmap.data(), w.len, pieces.data(), (int64_t)pieces.size(), (int32_t)n_long_, hist_.data(),
                        long_hist_.data(), sum.data(), host_threads());
     }
     size_t k = 0;
-    for (const Part& p : win.parts)
+    for (const GenomeWindow::Part& p : w.parts)
       for (int64_t s = p.start; s < p.end; s += FCSDP_PIECE_MAX, ++k) {
         DepthInterval& row = rows_[p.interval];
         row.total += sum[k].total, row.loci += sum[k].loci, row.above += sum[k].above;
@@ -314,88 +238,29 @@ class Run {
 
   const DepthJob& job_;
   int device_;
-  std::vector<std::string> bams_;
-  std::unique_ptr<BamReader> reader_;
-  size_t file_ = 0, chunk_ = 1;
-  BamHeader header_;
+  BamStream in_;
+  const BamHeader& header_;
+  size_t chunk_ = 1;
   std::vector<std::string> contigs_;
   fcsdp_params prm_{};
   bool include_ref_n_ = false;
-  int64_t window_bp_ = 1;
   std::vector<GenomeInterval> intervals_;
-  std::vector<Window> windows_;
+  std::vector<GenomeWindow> windows_;
   std::vector<DepthInterval> rows_;
   std::vector<int32_t> long_index_;
   size_t n_long_ = 0, cur_ = 0;
   std::map<size_t, std::vector<uint32_t>> open_;
   std::vector<uint64_t> hist_, long_hist_;
   uint64_t total_ = 0;
-  std::pair<int64_t, int64_t> last_key_{-1, -1};
   std::ofstream locus_;
   DepthRunStats st_;
 };
 
 }  // namespace
 
-std::vector<std::string> sorted_bam_inputs(const std::string& input) {
-  if (is_regular_file(input)) return {input};
-  if (!is_directory(input)) throw fileNotFound(input);
-  std::vector<std::string> names = list_dir(input, ".bam");
-  std::sort(names.begin(), names.end());
-  std::vector<std::string> out;
-  for (const std::string& n : names) out.push_back(n.find('/') == std::string::npos ? input + "/" + n : n);
-  if (out.empty()) throw fileNotFound(input + "/*.bam");
-  return out;
-}
-
-// The single distinct SM of the header's @RG lines.
-std::string single_sample(const BamHeader& h, const std::string& command) {
-  std::set<std::string> sm;
-  std::istringstream ss(h.text);
-  for (std::string line; std::getline(ss, line);) {
-    if (line.rfind("@RG", 0) != 0) continue;
-    for (size_t p = 0; p < line.size();) {
-      const size_t e = std::min(line.find('\t', p), line.size());
-      if (line.compare(p, 3, "SM:") == 0 && e > p + 3) sm.insert(line.substr(p + 3, e - p - 3));
-      p = e + 1;
-    }
-  }
-  if (sm.empty()) throw invalidParam("the BAM header names no sample (no @RG line with SM)");
-  if (sm.size() > 1) {
-    std::string all;
-    for (const std::string& s : sm) all += (all.empty() ? "" : ", ") + s;
-    throw invalidParam("the BAM header names " + std::to_string(sm.size()) + " samples (" + all + "); " + command + " takes one");
-  }
-  return *sm.begin();
-}
-
-// -L sorted by header contig order with overlapping and abutting intervals merged, or one interval per contig.
-std::vector<GenomeInterval> merged_intervals(const std::string& path, const BamHeader& h) {
-  std::vector<GenomeInterval> iv;
-  if (path.empty()) {
-    for (size_t c = 0; c < h.names.size(); ++c) iv.push_back({(int32_t)c, 0, h.lengths[c]});
-    return iv;
-  }
-  for (const Interval& i : read_regions(path)) {
-    const int c = h.ref_index(i.chrom);
-    if (c < 0) throw invalidParam("contig " + i.chrom + " of " + path + " is not in the BAM header");
-    const int64_t s = std::max<int64_t>(i.lb - 1, 0), e = std::min<int64_t>(i.ub, h.lengths[(size_t)c]);
-    if (s >= e) throw invalidParam("interval " + i.chrom + ":" + std::to_string(i.lb) + "-" + std::to_string(i.ub) + " of " + path +
-                                   " is empty or beyond its contig");
-    iv.push_back({(int32_t)c, s, e});
-  }
-  std::sort(iv.begin(), iv.end(), [](const GenomeInterval& a, const GenomeInterval& b) { return a.ref != b.ref ? a.ref < b.ref : a.start < b.start; });
-  std::vector<GenomeInterval> out;
-  for (const GenomeInterval& i : iv) {
-    if (!out.empty() && out.back().ref == i.ref && i.start <= out.back().end) out.back().end = std::max(out.back().end, i.end);
-    else out.push_back(i);
-  }
-  return out;
-}
-
 bool gpu_depth_available() {
   const DpApi& a = dp_api();
-  return a.count && a.stats && a.last_error;
+  return a.count && a.stats && last_error_entry();
 }
 
 std::vector<std::string> depth_output_files(const DepthJob& job) {

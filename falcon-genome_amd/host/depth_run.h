@@ -1,6 +1,8 @@
-// The depth command around the rules of depth.h: the sample, the reference and
-// the intervals, the streamed BAM chunks cut over windows of the genome, the
-// device calls (include/fcsdp.h) or the host path, and the seven text files.
+// The depth command around the rules of depth.h: the sorted stream, the sample,
+// the reference and the windows come from bam_stream.h; here a chunk of records
+// is counted into every window it overlaps by the device calls
+// (include/fcsdp.h) or the host path, a window the stream has passed is
+// summarised, and the seven text files are written.
 #pragma once
 
 #include <cstdint>
@@ -8,20 +10,6 @@
 #include <vector>
 
 namespace fcsg {
-
-struct BamHeader;
-
-// What the commands that stream one sorted BAM over windows of the genome share (depth, ug).
-// The input BAM, or the part BAMs of a directory in name order.
-std::vector<std::string> sorted_bam_inputs(const std::string& input);
-// The single distinct SM of the header's @RG lines; invalidParam without one or with several.
-std::string single_sample(const BamHeader& h, const std::string& command);
-struct GenomeInterval {
-  int32_t ref;
-  int64_t start, end;  // 0-based half-open
-};
-// -L sorted by header contig order with overlapping and abutting intervals merged, or one interval per contig.
-std::vector<GenomeInterval> merged_intervals(const std::string& path, const BamHeader& h);
 
 struct DepthJob {
   std::string ref;        // FASTA

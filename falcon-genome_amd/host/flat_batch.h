@@ -1,8 +1,10 @@
 // What the runners of the record-walking commands (markdup_run.cpp,
-// bqsr_run.cpp, depth_run.cpp, ug_run.cpp) share: records flattened into the
-// arrays of an fcsdp_batch / fcsug_batch / fcsbq_batch (the same field names),
-// the host pool's width, and the device entry points looked up in whatever
-// libfcship the process loaded.
+// bqsr_run.cpp, depth_run.cpp, ug_run.cpp) share on the way to the device:
+// records flattened into the arrays of an fcsdp_batch / fcsug_batch /
+// fcsbq_batch (the same field names), the host pool's width, the device entry
+// points looked up in whatever libfcship the process loaded, the choice between
+// the device and the host path, and a device call's failure as failedCommand.
+// How the records get here is bam_stream.h.
 #pragma once
 
 #include <dlfcn.h>
@@ -17,6 +19,7 @@
 
 #include "bam.h"
 #include "common.h"
+#include "fcship.h"
 
 namespace fcsg {
 
@@ -45,6 +48,11 @@ inline int device_or_host(int job_device, bool available, const char* log_line) 
   std::lock_guard<std::mutex> lk(mu);
   if (said.insert(log_line).second) std::fputs(log_line, stderr);
   return -1;
+}
+
+// A device call's status: anything but FCS_OK is a failedCommand that names the command, the call and the library's error.
+inline void device_check(int rc, const char* command, const char* call) {
+  if (rc != FCS_OK) throw failedCommand(std::string("[E::fcs-genome ") + command + "] " + call + ": " + last_error_entry()());
 }
 
 // Records as the arrays of a batch; absent qualities are 0xff bytes.

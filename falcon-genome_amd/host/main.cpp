@@ -413,6 +413,24 @@ int align_main(int argc, char** argv) {
   return 0;
 }
 
+// What the handlers of markdup, baserecal / printreads / bqsr, depth and ug share.
+// fileNotFound unless the path is a regular file (or, for an input of part BAMs, anything that exists).
+void require_path(const std::string& path, bool or_directory = false) {
+  if (!(or_directory ? path_exists(path) : is_regular_file(path))) throw fileNotFound(path);
+}
+
+// Without -f, the first of the command's output files that exists is refused.
+void refuse_existing(const Args& a, const std::vector<std::string>& outputs) {
+  if (a.has("force")) return;
+  for (const std::string& f : outputs)
+    if (path_exists(f)) throw invalidParam("output " + f + " exists (use -f)");
+}
+
+// The end of a command's stats line on stderr.
+void stats_tail(double seconds, bool on_device) {
+  std::cerr << ", " << seconds << " s (" << (on_device ? "GPU" : "host") << ")" << std::endl;
+}
+
 // `fcs-genome markdup -i in.bam -o out.bam` (reference src/worker-markdup.cpp,
 // which runs sambamba markdup): the whole BAM is read into memory, marked as
 // one batch (host/markdup.h) and written in its input order.  With
@@ -432,14 +450,14 @@ int markdup_main(int argc, char** argv) {
     throw;
   }
   const std::string input = a.get("input"), output = a.get("output");
-  if (!is_regular_file(input)) throw fileNotFound(input);
-  if (!a.has("force") && path_exists(output)) throw invalidParam("output " + output + " exists (use -f)");
+  require_path(input);
+  refuse_existing(a, {output});
   int device = -1;
   if (conf().get_bool("markdup.gpu")) device = slots().front();
   const MarkdupStats st = markdup_bam(input, output, device);
   std::cerr << "[fcs-genome markdup] " << st.examined << " records examined, " << st.pairs << " pairs, " << st.fragments
-            << " fragments, " << st.duplicates << " records flagged, " << st.seconds << " s ("
-            << (st.on_device ? "GPU" : "host") << ")" << std::endl;
+            << " fragments, " << st.duplicates << " records flagged";
+  stats_tail(st.seconds, st.on_device);
   return 0;
 }
 
@@ -475,23 +493,18 @@ int bqsr_main(int argc, char** argv, BqsrCommand cmd) {
   BqsrJob job;
   job.ref = a.get("ref"), job.input = a.get("input");
   if (a.has("intervalList")) job.intervals = a.get("intervalList");
-  if (!is_regular_file(job.ref)) throw fileNotFound(job.ref);
-  if (!path_exists(job.input)) throw fileNotFound(job.input);
-  if (!job.intervals.empty() && !is_regular_file(job.intervals)) throw fileNotFound(job.intervals);
+  require_path(job.ref), require_path(job.input, true);
+  if (!job.intervals.empty()) require_path(job.intervals);
   if (counts) {
     job.known = a.all("knownSites");
-    for (const std::string& k : job.known)
-      if (!is_regular_file(k)) throw fileNotFound(k);
+    for (const std::string& k : job.known) require_path(k);
   }
   const std::string output = a.get("output");
   if (cmd == BqsrCommand::kBaserecal) job.report = output;
   else job.output = output, job.report = a.get("bqsr");
-  if (cmd == BqsrCommand::kPrintreads && !is_regular_file(job.report)) throw fileNotFound(job.report);
-  if (!a.has("force")) {
-    if (path_exists(output)) throw invalidParam("output " + output + " exists (use -f)");
-    if (cmd == BqsrCommand::kBqsr && !job.report.empty() && path_exists(job.report))
-      throw invalidParam("output " + job.report + " exists (use -f)");
-  }
+  if (cmd == BqsrCommand::kPrintreads) require_path(job.report);
+  refuse_existing(a, cmd == BqsrCommand::kBqsr && !job.report.empty() ? std::vector<std::string>{output, job.report}
+                                                                      : std::vector<std::string>{output});
   if (conf().get_bool("bqsr.gpu")) job.device = slots().front();
   const BqsrStats st = cmd == BqsrCommand::kBaserecal ? baserecal_run(job)
                        : cmd == BqsrCommand::kPrintreads ? printreads_run(job) : bqsr_run(job);
@@ -500,7 +513,7 @@ int bqsr_main(int argc, char** argv, BqsrCommand cmd) {
     std::cerr << ", " << st.counted << " counted, " << st.observations << " observations, " << st.errors << " errors, "
               << st.known_sites << " known sites (" << st.known_skipped << " on unknown contigs)";
   if (applies) std::cerr << ", " << st.recalibrated << " recalibrated";
-  std::cerr << ", " << st.seconds << " s (" << (st.on_device ? "GPU" : "host") << ")" << std::endl;
+  stats_tail(st.seconds, st.on_device);
   return 0;
 }
 
@@ -537,17 +550,14 @@ int depth_main(int argc, char** argv) {
   }
   job.omit_base = a.has("omitBaseOutput"), job.omit_intervals = a.has("omitIntervals");
   job.omit_summary = a.has("omitSampleSummary");
-  if (!is_regular_file(job.ref)) throw fileNotFound(job.ref);
-  if (!path_exists(job.input)) throw fileNotFound(job.input);
-  if (!job.intervals.empty() && !is_regular_file(job.intervals)) throw fileNotFound(job.intervals);
-  if (!a.has("force"))
-    for (const std::string& f : depth_output_files(job))
-      if (path_exists(f)) throw invalidParam("output " + f + " exists (use -f)");
+  require_path(job.ref), require_path(job.input, true);
+  if (!job.intervals.empty()) require_path(job.intervals);
+  refuse_existing(a, depth_output_files(job));
   if (conf().get_bool("depth.gpu")) job.device = slots().front();
   const DepthRunStats st = depth_run(job);
   std::cerr << "[fcs-genome depth] sample " << st.sample << ": " << st.records << " records, " << st.intervals << " intervals, "
-            << st.windows << " windows, " << st.loci << " loci, total depth " << st.total << ", " << st.seconds << " s ("
-            << (st.on_device ? "GPU" : "host") << ")" << std::endl;
+            << st.windows << " windows, " << st.loci << " loci, total depth " << st.total;
+  stats_tail(st.seconds, st.on_device);
   return 0;
 }
 
@@ -579,17 +589,14 @@ int ug_main(int argc, char** argv) {
   if (a.has("skip-concat")) throw invalidParam("--skip-concat: one run is one stream and writes one VCF, there are no parts to keep");
   if (a.has("extra-options"))
     std::cerr << "[fcs-genome ug] --extra-options " << a.get("extra-options") << ": ignored (no GATK is run)" << std::endl;
-  if (!is_regular_file(job.ref)) throw fileNotFound(job.ref);
-  if (!path_exists(job.input)) throw fileNotFound(job.input);
-  if (!job.intervals.empty() && !is_regular_file(job.intervals)) throw fileNotFound(job.intervals);
-  if (!a.has("force"))
-    for (const std::string& f : ug_output_files(job))
-      if (path_exists(f)) throw invalidParam("output " + f + " exists (use -f)");
+  require_path(job.ref), require_path(job.input, true);
+  if (!job.intervals.empty()) require_path(job.intervals);
+  refuse_existing(a, ug_output_files(job));
   if (conf().get_bool("ug.gpu")) job.device = slots().front();
   const UgRunStats st = ug_run(job);
   std::cerr << "[fcs-genome ug] sample " << st.sample << ": " << st.records << " records, " << st.intervals << " intervals, "
-            << st.windows << " windows, " << st.sites << " sites, " << st.calls << " calls, " << st.seconds << " s ("
-            << (st.on_device ? "GPU" : "host") << ")" << std::endl;
+            << st.windows << " windows, " << st.sites << " sites, " << st.calls << " calls";
+  stats_tail(st.seconds, st.on_device);
   return 0;
 }
 

@@ -6,10 +6,10 @@
 #include <array>
 #include <cstdio>
 #include <cstring>
-#include <sstream>
 #include <string_view>
 #include <unordered_map>
 
+#include "bam_stream.h"
 #include "common.h"
 #include "fcship.h"
 #include "flat_batch.h"
@@ -45,7 +45,6 @@ namespace {
 
 struct DupApi {
   decltype(&fcsdup_mark) mark = FCSG_DEVICE_ENTRY(fcsdup_mark);
-  LastErrorFn last_error = last_error_entry();
 };
 
 const DupApi& dup_api() {
@@ -55,7 +54,7 @@ const DupApi& dup_api() {
 
 }  // namespace
 
-bool gpu_markdup_available() { return dup_api().mark && dup_api().last_error; }
+bool gpu_markdup_available() { return dup_api().mark && last_error_entry(); }
 
 MarkdupStats mark_duplicates(std::vector<BamRecord>& recs, const std::vector<int32_t>& lib, int32_t n_lib, int32_t n_ref,
                              int device) {
@@ -91,8 +90,7 @@ MarkdupStats mark_duplicates(std::vector<BamRecord>& recs, const std::vector<int
                      "duplicates are marked on the host\n") >= 0;
   if (on_device) {
     fcsdup_stats ds;
-    if (dup_api().mark(device, &b, dup.data(), &ds) != FCS_OK)
-      throw failedCommand(std::string("[E::fcs-genome markdup] fcsdup_mark: ") + dup_api().last_error());
+    device_check(dup_api().mark(device, &b, dup.data(), &ds), "markdup", "fcsdup_mark");
     st.examined = ds.examined, st.pairs = ds.pairs, st.fragments = ds.fragments, st.duplicates = ds.duplicates;
   } else {
     st = mark_duplicates_host(b, dup.data());
@@ -107,17 +105,8 @@ MarkdupStats mark_duplicates(std::vector<BamRecord>& recs, const std::vector<int
 
 int32_t libraries_of(const BamHeader& h, const std::vector<BamRecord>& recs, std::vector<int32_t>& lib) {
   std::unordered_map<std::string, int32_t> lib_of_name, lib_of_rg;
-  std::istringstream ss(h.text);
-  for (std::string line; std::getline(ss, line);) {
-    if (line.rfind("@RG", 0) != 0) continue;
-    std::string id, lb;
-    for (size_t p = 0; p < line.size();) {
-      const size_t e = std::min(line.find('\t', p), line.size());
-      const std::string f = line.substr(p, e - p);
-      if (f.rfind("ID:", 0) == 0) id = f.substr(3);
-      if (f.rfind("LB:", 0) == 0) lb = f.substr(3);
-      p = e + 1;
-    }
+  for (const RgLine& line : rg_lines(h)) {
+    const std::string id = line.get("ID"), lb = line.get("LB");
     if (id.empty()) continue;
     int32_t k = 0;
     if (!lb.empty()) k = lib_of_name.try_emplace(lb, (int32_t)lib_of_name.size() + 1).first->second;
@@ -134,10 +123,10 @@ int32_t libraries_of(const BamHeader& h, const std::vector<BamRecord>& recs, std
 }
 
 MarkdupStats markdup_bam(const std::string& input, const std::string& output, int device) {
-  BamReader in(input);
-  const BamHeader h = in.header();
+  BamStream in(input, false);
+  const BamHeader& h = in.header();
   std::vector<BamRecord> recs;
-  for (BamRecord r; in.next(r);) recs.push_back(std::move(r));
+  in.read(recs, SIZE_MAX);
   std::vector<int32_t> lib;
   const int32_t n_lib = libraries_of(h, recs, lib);
   const MarkdupStats st = mark_duplicates(recs, lib, n_lib, (int32_t)h.names.size(), device);

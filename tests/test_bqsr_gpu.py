@@ -7,6 +7,7 @@ import threading
 import numpy as np
 import pytest
 
+import bam_stream_cases as S
 import bqsr_cases as B
 import fcship
 import host_lib as H
@@ -302,3 +303,19 @@ def test_bqsr_command_gpu_and_host_write_identical_files(gpu, tmp_path):
     _, _, before = H.read_bam(d / "sample.bam")
     _, _, after = H.read_bam(tmp_path / "true.bam")
     assert sum(a["qual"] != b["qual"] for a, b in zip(before, after)) > 1000
+
+
+def test_bqsr_command_streams_a_part_directory_gpu_and_host_identical(gpu, tmp_path):
+    """Chunks of 128 records and a file boundary fall inside the data (bam_stream_cases); bqsr has no windows."""
+    ref, parts, n = S.part_directory(tmp_path)
+    logs = {}
+    for mode in ("false", "true"):
+        p = H.run_cli("bqsr", "-r", ref, "-i", parts, "-o", tmp_path / f"{mode}.bam", "-b", tmp_path / f"{mode}.grp",
+                      env={"FCS_BQSR_GPU": mode, "FCS_GPU_DEVICES": str(gpu), "FCS_BQSR_CHUNK_RECORDS": "128"}, cwd=tmp_path)
+        assert p.returncode == 0, p.stderr[-2000:]
+        logs[mode] = p.stderr.rstrip("\n").split("\n")[-1]
+    assert "(host)" in logs["false"] and "(GPU)" in logs["true"]
+    assert f"] {n} records, " in logs["true"], logs["true"]
+    for s in ("bam", "grp"):
+        assert (tmp_path / f"true.{s}").read_bytes() == (tmp_path / f"false.{s}").read_bytes(), s
+    assert int(logs["true"].split(" recalibrated")[0].split(", ")[-1]) > 0

@@ -7,6 +7,7 @@ import threading
 import numpy as np
 import pytest
 
+import bam_stream_cases as S
 import depth_cases as D
 import fcship
 import host_lib as H
@@ -280,3 +281,22 @@ def test_depth_command_gpu_and_host_write_identical_files(gpu, tmp_path):
     assert (tmp_path / "all_true").read_text().count("\n") == 200001
     total = int((tmp_path / "all_true.sample_summary").read_text().split("\n")[1].split("\t")[1])
     assert total > 1000000
+
+
+def test_depth_command_streams_a_part_directory_gpu_and_host_identical(gpu, tmp_path):
+    """Chunks of 128 records, a file boundary and windows of 1,024 loci all fall inside the data (bam_stream_cases)."""
+    ref, parts, n = S.part_directory(tmp_path)
+    suffixes = ["", ".sample_summary", ".sample_statistics", ".sample_cumulative_coverage_counts",
+                ".sample_cumulative_coverage_proportions", ".sample_interval_summary", ".sample_interval_statistics"]
+    logs = {}
+    for mode in ("false", "true"):
+        p = H.run_cli("depth", "-r", ref, "-i", parts, "-o", tmp_path / mode,
+                      env={"FCS_DEPTH_GPU": mode, "FCS_GPU_DEVICES": str(gpu), "FCS_DEPTH_CHUNK_RECORDS": "128",
+                           "FCS_DEPTH_WINDOW_BP": str(S.WINDOW_BP)}, cwd=tmp_path)
+        assert p.returncode == 0, p.stderr[-2000:]
+        logs[mode] = p.stderr.rstrip("\n").split("\n")[-1]
+    assert "(host)" in logs["false"] and "(GPU)" in logs["true"]
+    assert f": {n} records, 2 intervals, 12 windows, " in logs["true"], logs["true"]
+    for s in suffixes:
+        assert (tmp_path / f"true{s}").read_bytes() == (tmp_path / f"false{s}").read_bytes(), s
+    assert int(logs["true"].split("total depth ")[1].split(",")[0]) > 0

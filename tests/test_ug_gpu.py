@@ -6,6 +6,7 @@ import threading
 import numpy as np
 import pytest
 
+import bam_stream_cases as S
 import fcship
 import host_lib as H
 import ug_cases as U
@@ -272,3 +273,20 @@ def test_ug_command_gpu_and_host_write_identical_files(gpu, tmp_path):
         assert (tmp_path / f"true.vcf{s}").read_bytes() == (tmp_path / f"false.vcf{s}").read_bytes(), s
     calls = [ln for ln in (tmp_path / "true.vcf").read_text().splitlines() if not ln.startswith("#")]
     assert len(calls) >= 1 and "4 windows" in logs["true"]
+
+
+def test_ug_command_streams_a_part_directory_gpu_and_host_identical(gpu, tmp_path):
+    """Chunks of 128 records, a file boundary and windows of 1,024 loci all fall inside the data (bam_stream_cases)."""
+    ref, parts, n = S.part_directory(tmp_path)
+    logs = {}
+    for mode in ("false", "true"):
+        p = H.run_cli("ug", "-r", ref, "-i", parts, "-o", tmp_path / f"{mode}.vcf",
+                      env={"FCS_UG_GPU": mode, "FCS_GPU_DEVICES": str(gpu), "FCS_UG_CHUNK_RECORDS": "128",
+                           "FCS_UG_WINDOW_BP": str(S.WINDOW_BP)}, cwd=tmp_path)
+        assert p.returncode == 0, p.stderr[-2000:]
+        logs[mode] = p.stderr.rstrip("\n").split("\n")[-1]
+    assert "(host)" in logs["false"] and "(GPU)" in logs["true"]
+    assert f": {n} records, 2 intervals, 12 windows, " in logs["true"], logs["true"]
+    for s in ("", ".gz", ".gz.tbi"):
+        assert (tmp_path / f"true.vcf{s}").read_bytes() == (tmp_path / f"false.vcf{s}").read_bytes(), s
+    assert int(logs["true"].split(" sites, ")[1].split(" calls")[0]) > 0
