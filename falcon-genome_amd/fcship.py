@@ -1048,3 +1048,99 @@ def ug_sites(arrays, window, ref, table, min_baseq: int = 17, max_sites=None, de
     check(lib.fcsug_sites(device, C.addressof(b), C.addressof(prm), C.addressof(w), _ptr(ref), _ptr(table), _ptr(sites),
                           max_sites, C.addressof(n)))
     return sites[:n.value]
+
+
+# ---------------------------------------------------------------- joint genotyping (include/fcsjg.h)
+JG_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "fcsjg.h")
+FCSJG_SAMPLES_MAX, FCSJG_ALTS_MAX, FCSJG_PL_MAX, FCSJG_UNIT_BITS, FCSJG_S_ROWS, FCSJG_GENOTYPES_MAX = 1024, 6, (1 << 20) - 1, 20, 1282, 28
+FCSJG_KIND_BLOCK, FCSJG_KIND_CALL, FCSJG_NO_CALL = 0, 1, 255
+FCSJG_STATUS_FIELD, FCSJG_STATUS_PL = 1, 2
+
+
+class JgCohort(C.Structure):
+    _fields_ = [("n_samples", C.c_int32), ("reserved", C.c_int32), ("n_records", C.c_int64), ("rec_off", C.c_void_p),
+                ("beg", C.c_void_p), ("end", C.c_void_p), ("kind", C.c_void_p), ("alt", C.c_void_p), ("dp", C.c_void_p),
+                ("pl", C.c_void_p)]
+
+
+class JgSites(C.Structure):
+    _fields_ = [("n_sites", C.c_int64), ("pos", C.c_void_p), ("n_alt", C.c_void_p)]
+
+
+class JgModel(C.Structure):
+    _fields_ = [("S", C.c_void_p), ("LG", C.c_void_p), ("LP", C.c_void_p), ("min_qual", C.c_int64)]
+
+
+class JgOut(C.Structure):
+    _fields_ = [("q", C.c_void_p), ("mle", C.c_void_p), ("qual", C.c_void_p), ("kept", C.c_void_p), ("ac", C.c_void_p),
+                ("an", C.c_void_p), ("dp", C.c_void_p), ("pl_off", C.c_void_p), ("src", C.c_void_p), ("gt", C.c_void_p),
+                ("gq", C.c_void_p), ("pl", C.c_void_p), ("max_pl", C.c_int64), ("n_pl", C.c_void_p)]
+
+
+_sig("fcsjg_tables", C.c_int, [C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
+_sig("fcsjg_genotype", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+_sig("fcsjg_workspace_bytes", C.c_int64, [C.c_int64, C.c_int32])
+_sig("fcsjg_genotype_dev", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p, C.c_void_p])
+
+
+def jg_header_symbols() -> list[str]:
+    """Function names declared in include/fcsjg.h."""
+    import re
+    txt = re.sub(r"/\*.*?\*/", "", open(JG_HEADER_PATH).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(fcsjg_[a-z0-9_]+)\s*\(", txt)))
+
+
+# (name, dtype, entries per site, entries per (site, sample)) of fcsjg_out's arrays, in the struct's order
+JG_OUT_FIELDS = (("q", np.int64, 6, 0), ("mle", np.int32, 6, 0), ("qual", np.int64, 1, 0), ("kept", np.uint8, 1, 0),
+                 ("ac", np.int32, 6, 0), ("an", np.int32, 1, 0), ("dp", np.int64, 1, 0), ("pl_off", np.int64, 1, 0),
+                 ("src", np.int64, 0, 1), ("gt", np.uint8, 0, 2), ("gq", np.uint8, 0, 1))
+_JG_COHORT_DTYPES = (np.int64, np.int32, np.int32, np.uint8, np.uint8, np.int32, np.int32)
+
+
+def jg_tables(heterozygosity: float, n_samples: int):
+    """fcsjg_tables: (S[1282], LG[4 n + 1], LP[2 n + 1]) as int32."""
+    S, LG, LP = np.zeros(FCSJG_S_ROWS, np.int32), np.zeros(4 * n_samples + 1, np.int32), np.zeros(2 * n_samples + 1, np.int32)
+    check(lib.fcsjg_tables(heterozygosity, n_samples, S.ctypes.data, LG.ctypes.data, LP.ctypes.data))
+    return S, LG, LP
+
+
+def jg_cohort(rec_off, beg, end, kind, alt, dp, pl, n_samples=None, n_records=None):
+    """(fcsjg_cohort over host arrays, the arrays in its dtypes, which the caller keeps alive)."""
+    arrays = tuple(np.ascontiguousarray(a, t) for a, t in zip((rec_off, beg, end, kind, alt, dp, pl), _JG_COHORT_DTYPES))
+    c = JgCohort(len(arrays[0]) - 1 if n_samples is None else n_samples, 0, len(arrays[1]) if n_records is None else n_records,
+                 *(_ptr(a) for a in arrays))
+    return c, arrays
+
+
+def jg_out_arrays(n_sites: int, n_samples: int, max_pl: int, fill=0):
+    """{name: array} of fcsjg_out for n_sites x n_samples, pl of max_pl entries and n_pl of one."""
+    out = {name: np.full(n_sites * (per_site + per_cell * n_samples), fill, dt) for name, dt, per_site, per_cell in JG_OUT_FIELDS}
+    out["pl"] = np.full(max_pl, fill, np.int32)
+    out["n_pl"] = np.full(1, fill, np.int64)
+    return out
+
+
+def jg_out(arrays, max_pl=None) -> JgOut:
+    return JgOut(*(_ptr(arrays[name]) for name, *_ in JG_OUT_FIELDS), _ptr(arrays["pl"]),
+                 len(arrays["pl"]) if max_pl is None else max_pl, arrays["n_pl"].ctypes.data)
+
+
+def jg_genotype(cohort_arrays, pos, n_alt, tables, min_qual: int, max_pl=None, device: int = 0, entry=None, **kw):
+    """fcsjg_genotype: {name: array} of the outputs (pl cut to n_pl) for the cohort's arrays (rec_off, beg, end, kind,
+    alt, dp, pl[.][6]) and the sites; entry: another function of the same arguments after the device."""
+    c, keep = jg_cohort(*cohort_arrays, **kw)
+    pos, n_alt = np.ascontiguousarray(pos, np.int32), np.ascontiguousarray(n_alt, np.uint8)
+    S, LG, LP = (np.ascontiguousarray(t, np.int32) for t in tables)
+    st = JgSites(len(pos), _ptr(pos), _ptr(n_alt))
+    m = JgModel(_ptr(S), _ptr(LG), _ptr(LP), min_qual)
+    n = c.n_samples
+    max_pl = len(pos) * n * FCSJG_GENOTYPES_MAX if max_pl is None else max_pl
+    arrays = jg_out_arrays(len(pos), max(n, 0), max(max_pl, 0))
+    o = jg_out(arrays, max_pl)
+    if entry is None:
+        check(lib.fcsjg_genotype(device, C.addressof(c), C.addressof(st), C.addressof(m), C.addressof(o)))
+    else:
+        entry(C.addressof(c), C.addressof(st), C.addressof(m), C.addressof(o))
+    arrays["pl"] = arrays["pl"][:int(arrays["n_pl"][0])]
+    return arrays

@@ -24,6 +24,7 @@
 #include "seedext.h"
 #include "aligner.h"
 #include "intervals.h"
+#include "joint.h"
 #include "markdup.h"
 #include "sample_sheet.h"
 #include "vcf.h"
@@ -620,6 +621,24 @@ int fcsg_ug_vcf_header(const char* sample, const char* names, const int64_t* len
     rc = copy_out(ug_vcf_header(sample, contigs).to_text(), buf, cap);
   });
   return g ? g : rc;
+}
+
+// The host statement of joint genotyping (joint.h) over the arguments of
+// fcsjg_genotype (include/fcsjg.h): the tables with the threshold in units, and
+// the outputs of a cohort and its sites on `threads` threads.
+int fcsg_jg_tables(double heterozygosity, double stand_call_conf, int n_samples, int32_t* S, int32_t* LG, int32_t* LP,
+                   int64_t* min_qual) {
+  return guard([&] {
+    JointParams p;
+    p.heterozygosity = heterozygosity, p.stand_call_conf = stand_call_conf;
+    const JointTables t = joint_tables(p, n_samples);
+    std::copy(t.S.begin(), t.S.end(), S), std::copy(t.LG.begin(), t.LG.end(), LG), std::copy(t.LP.begin(), t.LP.end(), LP);
+    *min_qual = t.min_qual;
+  });
+}
+
+int fcsg_jg_genotype(const fcsjg_cohort* c, const fcsjg_sites* s, const fcsjg_model* m, int threads, const fcsjg_out* out) {
+  return guard([&] { joint_genotype_host(*c, *s, *m, threads, *out); });
 }
 
 int fcsg_bam_index(const char* bam) {

@@ -85,6 +85,11 @@ void Config::init(const std::string& root_dir) {
   declare("ug.heterozygosity", "0.001", "ug: the genotype prior's heterozygosity");
   declare("ug.pcr_error", "0.0001", "ug: the PCR error rate folded into every base's error");
   declare("ug.max_deletion_fraction", "0.05", "ug: sites where more than this fraction of the reads has a deletion are not called");
+  declare("joint.gpu", "false", "genotype sites on the GPU (fcsjg_genotype) instead of on the host (joint)");
+  declare("joint.stand_call_conf", "10", "joint: sites with a lower QUAL are not written");
+  declare("joint.heterozygosity", "0.001", "joint: the allele-count prior's heterozygosity");
+  declare("joint.max_alt", "6", "joint: ALTs kept per site, the most named first (at most 6)");
+  declare("joint.chunk_sites", "0", "joint: sites per genotyping call (0: as many as return 2^24 PLs at most)");
   // caller knobs (GATK HaplotypeCaller / Mutect2 argument defaults)
   declare("htc.min_base_quality", "10", "min base quality counted as evidence of activity");
   declare("htc.base_quality_threshold", "18", "PairHMM: base quals below this become 6");

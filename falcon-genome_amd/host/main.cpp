@@ -29,6 +29,7 @@
 #include "aligner.h"
 #include "bqsr_run.h"
 #include "depth_run.h"
+#include "joint_run.h"
 #include "ug_run.h"
 #include "intervals.h"
 #include "markdup.h"
@@ -600,6 +601,46 @@ int ug_main(int argc, char** argv) {
   return 0;
 }
 
+// `fcs-genome joint` (reference src/worker-joint.cpp, which runs GATK's
+// CombineGVCFs and GenotypeGVCFs per shard and concatenates the shards' VCFs):
+// the directory's one-sample GVCFs stream through host/joint_run.h a contig at
+// a time, combined into a site table and genotyped on the GPU (joint.gpu=true,
+// include/fcsjg.h) or on the host.  With joint.gpu=false the command needs no GPU.
+int joint_main(int argc, char** argv) {
+  Args a;
+  common_opts(a);
+  a.add("ref", "r", false, true, "reference genome path");
+  a.add("input-dir", "i", false, true, "directory of one-sample GVCFs (*.gvcf.gz, *.g.vcf.gz, *.gvcf, *.g.vcf), taken in name order");
+  a.add("output", "o", false, true, "output VCF file (<output>.gz and <output>.gz.tbi are written beside it)");
+  a.add("sample-id", "", false, false, "sample tag for log files");
+  a.add("database_name", "", false, false, "database name (accepted and ignored: no GenomicsDB is written)");
+  a.add("combine-only", "c", true, false, "stop after the combine step (refused: no combined GVCF is written)");
+  a.add("skip-combine", "g", true, false, "start from a combined GVCF (refused: none is read)");
+  try {
+    a.parse(argc, argv);
+  } catch (helpRequest&) {
+    std::cerr << "'fcs-genome joint' options:\n" << a.help();
+    throw;
+  }
+  JointJob job;
+  job.ref = a.get("ref"), job.input = a.get("input-dir"), job.output = a.get("output");
+  if (a.has("sample-id")) (void)a.get("sample-id");
+  if (a.has("combine-only")) throw invalidParam("--combine-only: the combine step keeps its table in memory, no combined GVCF is written");
+  if (a.has("skip-combine")) throw invalidParam("--skip-combine: the input is a directory of one-sample GVCFs, no combined GVCF is read");
+  if (a.has("database_name"))
+    std::cerr << "[fcs-genome joint] --database_name " << a.get("database_name") << ": ignored (no GenomicsDB is written)" << std::endl;
+  require_path(job.ref);
+  if (!is_directory(job.input)) throw fileNotFound(job.input + " (a directory of GVCFs)");
+  refuse_existing(a, joint_output_files(job));
+  if (conf().get_bool("joint.gpu")) job.device = slots().front();
+  const JointRunStats st = joint_run(job);
+  std::cerr << "[fcs-genome joint] " << st.samples << " samples, " << st.records << " records, " << st.sites << " sites, "
+            << st.written << " written, " << st.clamped << " PLs clamped, " << st.ignored << " calls ignored, " << st.cut
+            << " ALTs cut";
+  stats_tail(st.seconds, st.on_device);
+  return 0;
+}
+
 // `fcs-genome index -r ref.fasta`: the aligner's FMD-index, saved next to the
 // FASTA (<ref>.fcsidx) so that align maps it instead of building one per run
 // (bwa-flow reads the prebuilt bwa index; the reference expects it beside the
@@ -734,6 +775,7 @@ int print_help() {
                "  depth           depth of coverage of a BAM per locus, interval and sample (GPU difference array + scan)\n"
                "  ug              SNP calling from the pileup, UnifiedGenotyper-style (GPU pileup in LDS tiles)\n"
                "  htc             variant calling, HaplotypeCaller-style (GPU PairHMM)\n"
+               "  joint           joint genotyping of htc's GVCFs (GPU exact allele-frequency model)\n"
                "  mutect2         somatic variant calling, tumor/normal (GPU PairHMM)\n"
                "  conf            print configuration keys\n"
                "  index           build the aligner's FMD-index of a reference (<ref>.fcsidx)\n"
@@ -778,6 +820,7 @@ int main(int argc, char** argv) {
     else if (cmd == "bqsr") ret = bqsr_main(argc - 1, argv + 1, BqsrCommand::kBqsr);
     else if (cmd == "depth") ret = depth_main(argc - 1, argv + 1);
     else if (cmd == "ug" || cmd == "unifiedgeno") ret = ug_main(argc - 1, argv + 1);
+    else if (cmd == "joint") ret = joint_main(argc - 1, argv + 1);
     else if (cmd == "synth") ret = synth_main(argc - 1, argv + 1);
     else if (cmd == "index") ret = index_main(argc - 1, argv + 1);
     else if (cmd == "conf") {
