@@ -39,6 +39,7 @@ namespace {
 
 constexpr int kFmdBlock = 256;
 constexpr int kFmdMaxUnits = 32768;  // quads in flight: 256 CUs x 8 waves x 16
+constexpr int kFmdLocateMaxBlocks = 256 * 8;  // fmd_locate_kernel: a lane per row
 
 template <int C>
 __device__ __forceinline__ int64_t quad_bcast(int64_t v) {
@@ -149,7 +150,7 @@ int launch_fmd_collect(const FmdDevIndex& dx, const uint8_t* codes, int64_t n_co
 int launch_fmd_locate(const FmdDevIndex& dx, const int64_t* rows, int64_t n, int32_t max_steps, int64_t* pos,
                       int32_t* status, hipStream_t s) {
   if (n <= 0) return FCS_OK;
-  const int blocks = (int)std::min<int64_t>((n + kFmdBlock - 1) / kFmdBlock, 256 * 8);
+  const int blocks = (int)std::min<int64_t>((n + kFmdBlock - 1) / kFmdBlock, kFmdLocateMaxBlocks);
   hipLaunchKernelGGL(fmd_locate_kernel, dim3(blocks), dim3(kFmdBlock), 0, s, dx, rows, n, max_steps, pos, status);
   FCS_HIP_CHECK(hipGetLastError());
   return FCS_OK;

@@ -47,6 +47,9 @@ constexpr int kSeedOrderBlock = 64;  // one wave
 constexpr int kSeedTile = 64;        // SMEMs of a read staged in LDS at a time
 constexpr int kSeedBlock = 256;
 constexpr int kSeedScanBlock = 1024;
+constexpr int kSeedOrderMaxBlocks = 256 * 64;  // fmd_seed_order_kernel: a wave of four reads per block
+constexpr int kSeedExpandMaxBlocks = 256 * 8;  // fmd_seed_expand_kernel: 16 reads per block
+constexpr int kSeedLocateMaxBlocks = 256 * 8;  // fmd_seed_locate_kernel: a lane per located row
 
 // One lane reads the whole occ line (fmd_seed.hip's policy for its locate kernel).
 struct FmdLaneWords {
@@ -214,7 +217,7 @@ int launch_fmd_seed(const FmdDevIndex& dx, const FmdIv* slots, int32_t max_mems,
                     int32_t* n_eff, int64_t* n_rows, int64_t* mem_off, int64_t* row_off, FmdIv* mems, int64_t mem_cap,
                     int64_t* rows, int64_t* pos, int64_t row_cap, hipStream_t s) {
   if (n_reads > 0) {
-    const int blocks = (int)std::min<int64_t>(((int64_t)n_reads + 3) / 4, 256 * 64);
+    const int blocks = (int)std::min<int64_t>(((int64_t)n_reads + 3) / 4, kSeedOrderMaxBlocks);
     hipLaunchKernelGGL(fmd_seed_order_kernel, dim3(blocks), dim3(kSeedOrderBlock), 0, s, slots, max_mems, n_mems,
                        overflow, n_reads, max_occ, place, n_eff, n_rows);
     FCS_HIP_CHECK(hipGetLastError());
@@ -225,12 +228,12 @@ int launch_fmd_seed(const FmdDevIndex& dx, const FmdIv* slots, int32_t max_mems,
   if (n_reads <= 0) return FCS_OK;
   const bool walk = dx.sa != nullptr;  // without a device suffix array the encoded rows are the answer
   constexpr int per_block = kSeedBlock / kSeedRow;
-  const int blocks = (int)std::min<int64_t>(((int64_t)n_reads + per_block - 1) / per_block, 256 * 8);
+  const int blocks = (int)std::min<int64_t>(((int64_t)n_reads + per_block - 1) / per_block, kSeedExpandMaxBlocks);
   hipLaunchKernelGGL(fmd_seed_expand_kernel, dim3(blocks), dim3(kSeedBlock), 0, s, slots, max_mems, n_eff, place,
                      n_reads, max_occ, mem_off, row_off, mems, mem_cap, walk ? rows : pos, row_cap, walk ? 0 : 1);
   FCS_HIP_CHECK(hipGetLastError());
   if (walk && row_cap > 0) {
-    const int lblocks = (int)std::min<int64_t>((row_cap + kSeedBlock - 1) / kSeedBlock, 256 * 8);
+    const int lblocks = (int)std::min<int64_t>((row_cap + kSeedBlock - 1) / kSeedBlock, kSeedLocateMaxBlocks);
     hipLaunchKernelGGL(fmd_seed_locate_kernel, dim3(lblocks), dim3(kSeedBlock), 0, s, dx, rows, mem_off + n_reads,
                        mem_cap, row_off + n_reads, row_cap, max_steps, pos);
     FCS_HIP_CHECK(hipGetLastError());

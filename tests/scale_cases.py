@@ -5,6 +5,8 @@ every single-block scan, and at chr1-sized coordinates.
 - CAPS: the launch caps as the .hip sources state them (PINNED: where and how
   each is read), and SHAPES: every scale shape, derived from CAPS.
   tests/test_scale_cpu.py fails when a source no longer says what CAPS says.
+  The FMD seeding kernels' caps and shapes are here too; their
+  inputs are tests/fmd_scale_cases.py.
 - Sparse-wide inputs: a few thousand mixed-CIGAR records of the existing
   generators in bands around the tile boundaries of a very long window; the
   Python restatements (depth_cases, ug_cases) are their reference.
@@ -28,7 +30,10 @@ CSRC = os.path.join(ROOT, "falcon-genome_amd", "csrc")
 
 # ------------------------------------------------------------------ the caps and the shapes
 CAPS = dict(ug_max_blocks=2048, ug_block=256, dp_max_blocks=4096, dp_tile=4 * 256, bq_max_blocks=2048, bq_min_slice=32,
-            md_max_blocks=256 * 8, md_ends_blocks=256 * 32, bq_replica_bytes=64 << 20, bq_replica_max=16)
+            md_max_blocks=256 * 8, md_ends_blocks=256 * 32, bq_replica_bytes=64 << 20, bq_replica_max=16,
+            fmd_max_units=32768, fmd_block=256, fmd_locate_max_blocks=256 * 8, seed_row=16, seed_order_block=64,
+            seed_block=256, seed_scan_block=1024, seed_order_max_blocks=256 * 64, seed_expand_max_blocks=256 * 8,
+            seed_locate_max_blocks=256 * 8)
 
 # name: (source, pattern with one group, the group's text, the shapes to look at again)
 PINNED = dict(
@@ -49,6 +54,16 @@ PINNED = dict(
                     "256 * 32", "md_ends"),
     bq_replica_bytes=("bqsr.hip", r"\(\(size_t\)(64 << 20)\) / one\)", "64 << 20", "bq_rg"),
     bq_replica_max=("bqsr.hip", r"/ one\), 1, (\d+)\);", "16", "bq_rg"),
+    fmd_max_units=("fmd_seed.hip", r"constexpr int kFmdMaxUnits = ([^;]+);", "32768", "fmd_units, fmd_reads"),
+    fmd_block=("fmd_seed.hip", r"constexpr int kFmdBlock = ([^;]+);", "256", "fmd_locate, fmd_rows"),
+    fmd_locate_max_blocks=("fmd_seed.hip", r"constexpr int kFmdLocateMaxBlocks = ([^;]+);", "256 * 8", "fmd_locate, fmd_rows"),
+    seed_row=("fmd_seeds.hip", r"constexpr int kSeedRow = ([^;]+);", "16", "fmd_expand, fmd_order, fmd_reads"),
+    seed_order_block=("fmd_seeds.hip", r"constexpr int kSeedOrderBlock = ([^;]+);", "64", "fmd_order, fmd_reads"),
+    seed_block=("fmd_seeds.hip", r"constexpr int kSeedBlock = ([^;]+);", "256", "fmd_expand, fmd_seed_locate"),
+    seed_scan_block=("fmd_seeds.hip", r"constexpr int kSeedScanBlock = ([^;]+);", "1024", "fmd_scan_per, fmd_scan_empty"),
+    seed_order_max_blocks=("fmd_seeds.hip", r"constexpr int kSeedOrderMaxBlocks = ([^;]+);", "256 * 64", "fmd_order, fmd_reads"),
+    seed_expand_max_blocks=("fmd_seeds.hip", r"constexpr int kSeedExpandMaxBlocks = ([^;]+);", "256 * 8", "fmd_expand"),
+    seed_locate_max_blocks=("fmd_seeds.hip", r"constexpr int kSeedLocateMaxBlocks = ([^;]+);", "256 * 8", "fmd_seed_locate"),
 )
 
 
@@ -84,7 +99,17 @@ def _shapes():
         bq_count=c["bq_max_blocks"] * c["bq_min_slice"] + c["bq_max_blocks"] + 7,
         bq_check=c["bq_max_blocks"] * 256 + 256 + 5,
         bq_rg=(6, 90),
+        # FMD seeding: reads or rows one launch of each kernel covers in its first trip
+        fmd_units=c["fmd_max_units"],                                                  # fmd_collect_kernel: a read per quad
+        fmd_expand=c["seed_expand_max_blocks"] * (c["seed_block"] // c["seed_row"]),   # fmd_seed_expand_kernel
+        fmd_order=c["seed_order_max_blocks"] * (c["seed_order_block"] // c["seed_row"]),   # fmd_seed_order_kernel
+        fmd_locate=c["fmd_locate_max_blocks"] * c["fmd_block"],                        # fmd_locate_kernel
+        fmd_seed_locate=c["seed_locate_max_blocks"] * c["seed_block"],                 # fmd_seed_locate_kernel
     )
+    s["fmd_reads"] = max(s["fmd_order"], 2 * s["fmd_units"], 2 * s["fmd_expand"]) + 1 + 3   # past every per-read cap
+    s["fmd_rows"] = s["fmd_locate"] + 257
+    s["fmd_scan_per"] = -(-s["fmd_reads"] // c["seed_scan_block"])                     # reads per lane of the scan
+    s["fmd_scan_empty"] = c["seed_scan_block"] - -(-s["fmd_reads"] // s["fmd_scan_per"])   # trailing lanes without a read
     s["ug_tiles"] = -(-s["ug_window"] // ub)
     s["dp_tiles"] = -(-s["dp_window"] // dt)
     s["bq_count_slice"] = -(-s["bq_count"] // c["bq_max_blocks"])
