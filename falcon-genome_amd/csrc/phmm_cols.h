@@ -62,7 +62,13 @@
 //   * phmm6_kernel (the one every class launches): the first dequeue and the
 //     early exit, and Cols1Queue (the circular segment table filled from a
 //     per-class queue by a persistent grid, streams that end when the class
-//     is exhausted).
+//     is exhausted).  Each class is compiled and launched for its own number
+//     of waves per SIMD, cols6_waves(C): 3 for every class, see there.
+// The body holds little besides the 2 C floats of state across its pass loop
+// (DESIGN §4.1j): the staged ring row waits as two packed dwords (PackedRow),
+// and the segment table keeps pair, R, H, first row and read offset only; the
+// haplotype offset and the first row's scale 2^120 / H are read again from
+// the table's pair at the block tops that need them, once per pair.
 // That the two compute the same bits per step is therefore structural: there
 // is one step.  What the tests hold equal is the rest: the stream mechanics of
 // phmm6 against phmm5 on the same batch (tests/test_pairhmm_queue_gpu.py), and
@@ -637,9 +643,10 @@ constexpr int kCols1CapOff = kCols1Chunks * kCols1ChunkBytes;  // lane 15's E pe
 constexpr int kCols1TabOff = kCols1CapOff + 4 * 16 * 4;
 constexpr int kCols1Lds = kCols1TabOff + 3 * 128 * 4;
 constexpr int kCols1MaxK = 16;  // pairs per stream: one per lane of the segment table
-// Waves per SIMD the kernel is compiled for: what its registers allow without
-// scratch (tools/kernel_resources.py: 134 VGPRs at C = 11 .. 168 at C = 19, so
-// every class takes 3; 4 waves need <= 128 and spilled 16 .. 84 bytes per lane).
+// Waves per SIMD phmm5 is compiled for: what its registers allow without
+// scratch (tools/kernel_resources.py: 127 VGPRs at C = 11 .. 163 at C = 19 with
+// the staged row packed, DESIGN §4.1j, so every class takes 3; phmm6 has its
+// own table, cols6_waves below).
 __host__ __device__ constexpr int cols1_waves(int C) { return 3; }
 static_assert(kCols1Lds <= 10240, "16 waves per CU");
 
@@ -664,12 +671,33 @@ __device__ __forceinline__ void cols1_put(unsigned char* smem, int slot, int seg
 // converted, and when the streams end.
 constexpr int kNever = 0x3FFFFFFF;  // a stream row that never comes
 
+// A staged row as it waits between stage A and the next block's stage B: the
+// seven bytes of a RawRow and the row's own insertion quality in two dwords
+// (own = rb | bq << 8 | dq << 16 | gq << 24, below = niq | ndq << 8 | ngq << 16 |
+// own iq << 24) instead of eight registers held across the pass loop.  Every
+// consumer masks the qualities with 127 and reads rb as an unsigned char, so
+// the unpacked row builds the same item bit for bit.  A row that is no read
+// row (role 0 or 4) is never unpacked into row_params: its words are 0.
+struct PackedRow {
+  uint32_t own, below;
+};
+__device__ __forceinline__ PackedRow cols1_pack(const RawRow& r, int oiq) {
+  return PackedRow{(uint32_t)(r.rb & 255) | (uint32_t)(r.bq & 255) << 8 | (uint32_t)(r.dq & 255) << 16 |
+                       (uint32_t)r.gq << 24,
+                   (uint32_t)(r.niq & 255) | (uint32_t)(r.ndq & 255) << 8 | (uint32_t)(r.ngq & 255) << 16 |
+                       (uint32_t)oiq << 24};
+}
+__device__ __forceinline__ RawRow cols1_unpack(const PackedRow& w) {
+  return RawRow{(int)(w.own & 255u),         (int)((w.own >> 8) & 255u),    (int)((w.own >> 16) & 255u), (int)(w.own >> 24),
+                (int)(w.below & 255u),       (int)((w.below >> 8) & 255u),  (int)((w.below >> 16) & 255u)};
+}
+__device__ __forceinline__ int cols1_own_iq(const PackedRow& w) { return (int)(w.below >> 24); }
+
 // One entry of a segment table: lane sl of a segment holds the pair of slot
 // sl of that segment's stream, G = the pair's first stream row.
 struct Cols1Seg {
   int pm, Rm, Hm, Gm;
-  int64_t rom, hom;
-  float Im;
+  int64_t rom;
 };
 
 // The match tables copied to LDS for the ring items (every lane of the wave calls it).
@@ -701,8 +729,8 @@ struct Cols1Batch {
 };
 
 // ---- phmm6's feed: CONTINUOUS streams fed from a per-class queue (DESIGN
-// §4.1g).  A class launch is one round of the chip (CUs x 4 SIMDs x 3
-// waves, each a workgroup), and a wave's four streams run until the class is
+// §4.1g).  A class launch is one round of the chip (CUs x 4 SIMDs x
+// cols6_waves(C) waves, each a workgroup), and a wave's four streams run until the class is
 // exhausted: no batches, so no drain, no ring prologue and no segment-table
 // scan between pairs, no one-pair tail, and no workgroups that find nothing.
 //   * The class's pairs order[bounds[cls] .. bounds[cls + 1]) are handed out
@@ -729,9 +757,19 @@ struct Cols1Batch {
 //     the wave ends at the block top after its last capture.
 // The streams run in cols1_stream; this is its feed.
 constexpr int kCols6Lds = kCols1Lds;
-constexpr int kCols6Waves = 3;   // per SIMD: the grid is CUs x 4 x kCols6Waves workgroups
+// Waves per SIMD of class C's launch: the kernel is compiled for that bound and
+// the grid is CUs x 4 x cols6_waves(C) one-wave workgroups.  C <= 17 fit a
+// fourth wave (<= 128 VGPRs, no scratch, under bound 4; C = 19 is 5 dwords
+// short), but the fourth wave bought nothing measurable on C2 (DESIGN §4.1j:
+// `C <= 14 ? 4 : 3` and `C <= 17 ? 4 : 3` ran within +-0.4% of this table; at
+// 3 waves the step already issues at the rate §4.1e measured for 8), so every
+// class stays at 3.
+__host__ __device__ constexpr int cols6_waves(int C) { return 3; }
 constexpr int kCols6Ahead = 48;  // rows located ahead of stage A below which a stream asks for its next pair
-static_assert(kCols6Lds <= 13653, "12 waves per CU");
+constexpr bool cols6_lds_fits(int C) { return cols6_waves(C) >= 4 ? kCols6Lds <= 10240 : kCols6Lds <= 13653; }
+static_assert(cols6_lds_fits(11) && cols6_lds_fits(12) && cols6_lds_fits(13) && cols6_lds_fits(14) &&
+                  cols6_lds_fits(15) && cols6_lds_fits(16) && cols6_lds_fits(17) && cols6_lds_fits(19),
+              "16 waves per CU share 163,840 B at 4 per SIMD, 12 at 3");
 
 struct Cols1Queue {
   static constexpr bool kQueue = true;
@@ -760,8 +798,7 @@ struct Cols1Queue {
   // position past the class closes the stream.  The pair starts at row
   // max(gend, gmin), gmin = the first row stage A has not located, in slot
   // nq mod 16 of the table, whose `other` bit it clears.
-  __device__ __forceinline__ void complete(int gmin, const PhmmDevBatch& b, const PhmmTables<float>& tab, Cols1Seg& tb,
-                                           unsigned& other) {
+  __device__ __forceinline__ void complete(int gmin, const PhmmDevBatch& b, Cols1Seg& tb, unsigned& other) {
     const int seg = threadIdx.x >> 4, sl = threadIdx.x & 15;
     const long long base = (long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)qv);
     const bool mine = (pend >> seg) & 1u;
@@ -778,8 +815,6 @@ struct Cols1Queue {
         tb.Rm = R;
         tb.Hm = H;
         tb.rom = b.read_off[ri];
-        tb.hom = b.hap_off[hi];
-        tb.Im = tab.init_const / (float)H;
         tb.Gm = G;
       }
       other &= ~(1u << (nq & 15));
@@ -823,7 +858,6 @@ __device__ __forceinline__ void cols1_stream(const PhmmDevBatch& b, const PhmmTa
   auto tR = [&](int k) { return bp(tb.Rm, k); };
   auto tH = [&](int k) { return bp(tb.Hm, k); };
   auto tP = [&](int k) { return bp(tb.pm, k); };
-  auto tI = [&](int k) { return __int_as_float(bp(__float_as_int(tb.Im), k)); };
   auto t64 = [&](int64_t v, int k) {
     const int lo = bp((int)v, k), hi = bp((int)(v >> 32), k);
     return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
@@ -848,10 +882,13 @@ __device__ __forceinline__ void cols1_stream(const PhmmDevBatch& b, const PhmmTa
     const bool ok = valid(k);
     const int Hk = tH(k);
     const int H = ok ? Hk : 0;
-    const int64_t ho = t64(tb.hom, k);
+    // the haplotype's offset is not held in the table: it is read again from
+    // the pair here, once per pair and stream
+    const int pk = tP(k);
+    const int64_t ho = ok ? b.hap_off[b.pair_hap[pk]] : 0;
     uint32_t raw[NW + 1];
     int al;
-    cols_load<NW>(b.hb, ok ? ho : 0, H, i0, raw, al);
+    cols_load<NW>(b.hb, ho, H, i0, raw, al);
     bool oth = false;
     cols_convert<NW>(raw, al, i0, H, dst, oth);
     const unsigned long long bal = __ballot(oth && ok);
@@ -870,18 +907,15 @@ __device__ __forceinline__ void cols1_stream(const PhmmDevBatch& b, const PhmmTa
 
   // The ring's items (row base + sl per lane) in two stages one block apart.
   int kp = 0;  // stage A's cursor: the pair holding this lane's item row
-  RawRow praw{-1, 0, 0, 0, 0, 0, 0};
-  int prole = 0;  // role | first << 4 | the row's own insertion quality << 8
-  float pih = 0.f;
+  PackedRow praw{0u, 0u};  // the row's bytes and its own insertion quality (cols1_pack)
+  int prole = 0;  // role | first << 4
   bool kok = false, nok = false;
   int kG = 0, kR = 0, nG = 0;
-  float kI = 0.f;
   int64_t kro = 0;
   auto load_cursor = [&] {
     kok = valid(kp);
     kG = tG(kp);
     kR = tR(kp);
-    kI = tI(kp);
     kro = t64(tb.rom, kp);
     nok = valid(kp + 1);
     nG = tG(kp + 1);
@@ -897,17 +931,20 @@ __device__ __forceinline__ void cols1_stream(const PhmmDevBatch& b, const PhmmTa
     int role = 0;
     if (kok && r >= 0 && r < kR) role = r == kR - 1 ? 3 : 2;
     else if (kok && r == kR) role = 4;
-    pih = kI;
     prole = role | (r == 0 ? 16 : 0);
-    praw = (role == 2 || role == 3) ? load_raw(b, kR, kro, r) : RawRow{-1, 0, 0, 0, 0, 0, 0};
-    if (role == 2 || role == 3) prole |= (int)b.iq[kro + r] << 8;
+    praw = (role == 2 || role == 3) ? cols1_pack(load_raw(b, kR, kro, r), b.iq[kro + r]) : PackedRow{0u, 0u};
   };
-  // kp is still the cursor stage A left for this item: a hazard row sets its
-  // pair's bit of `other` in every lane of the segment (rare: one branch).
+  // kp is still the cursor stage A left for this item.  A pair's first row
+  // takes its scale 2^120 / H from the table here, once per pair and stream,
+  // so no lane holds it across the pass loop; a hazard row sets its pair's bit
+  // of `other` in every lane of the segment (rare: one branch each).
   auto stage_b = [&](int base) {  // base >= 0
     bool hz;
+    const bool first = (prole & 16) != 0;
+    float ih = 0.f;
+    if (__ballot(first) != 0ull) ih = tab.init_const / (float)tH(kp);  // uniform: tH shuffles
     cols1_put(smem_raw, (int)((unsigned)(base + sl) % (unsigned)kCols1Ring), seg,
-              cols_item(tab, praw, prole >> 8, prole & 15, (prole & 16) != 0, pih, hz));
+              cols_item(tab, cols1_unpack(praw), cols1_own_iq(praw), prole & 15, first, ih, hz));
     if (__ballot(hz) != 0ull) {  // uniform
       unsigned m = hz ? 1u << Feed::bit(kp) : 0u;
 #pragma unroll
@@ -919,7 +956,7 @@ __device__ __forceinline__ void cols1_stream(const PhmmDevBatch& b, const PhmmTa
   // to the wave's first request, a batch's are in the table and their codes
   // are converted here.
   if constexpr (Feed::kQueue) {
-    feed.complete(0, b, tab, tb, other);
+    feed.complete(0, b, tb, other);
   } else {
     fetch_codes(0, nxt);
     nk = 0;
@@ -951,7 +988,7 @@ __device__ __forceinline__ void cols1_stream(const PhmmDevBatch& b, const PhmmTa
     // the next request.
     if constexpr (Feed::kQueue) {
       if (feed.pend != 0u) {  // uniform
-        feed.complete(t0 + 32, b, tab, tb, other);
+        feed.complete(t0 + 32, b, tb, other);
         load_cursor();
         load_cap();
       }
@@ -1148,14 +1185,12 @@ __global__ __launch_bounds__(64, cols1_waves(C)) void phmm5_kernel(
     // Segment table: lane sl holds pair sl of the segment's stream (stream seg
     // of the batch takes every 4th pair).
     const long long idx = bstart + seg + 4LL * sl;
-    Cols1Seg tb{(sl < Kb && idx < bend) ? order[idx] : -1, 0, 0, 0, 0, 0, 0.f};
+    Cols1Seg tb{(sl < Kb && idx < bend) ? order[idx] : -1, 0, 0, 0, 0};
     if (tb.pm >= 0) {
       const int ri = b.pair_read[tb.pm], hi = b.pair_hap[tb.pm];
       tb.Rm = b.read_len[ri];
       tb.Hm = b.hap_len[hi];
       tb.rom = b.read_off[ri];
-      tb.hom = b.hap_off[hi];
-      tb.Im = tab.init_const / (float)tb.Hm;
     }
     const int len = tb.pm >= 0 ? tb.Rm + 2 : 0;  // rows 1..R, V, Z
     int incl = len;
@@ -1174,7 +1209,7 @@ __global__ __launch_bounds__(64, cols1_waves(C)) void phmm5_kernel(
 
 // phmm6: one persistent wave per workgroup, its streams fed by Cols1Queue.
 template <int C>
-__global__ __launch_bounds__(64, kCols6Waves) void phmm6_kernel(
+__global__ __launch_bounds__(64, cols6_waves(C)) void phmm6_kernel(
     const PhmmDevBatch b, const int32_t* __restrict__ order, const int64_t* __restrict__ bounds, const int cls,
     const PhmmTables<float> gtab, double* __restrict__ out, int32_t* __restrict__ rescue_list,
     unsigned long long* __restrict__ rescue_count, const float thr, const int use_rescue,
@@ -1189,7 +1224,7 @@ __global__ __launch_bounds__(64, kCols6Waves) void phmm6_kernel(
   if ((long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)qv) >= count) return;
   const PhmmTables<float> tab = cols1_tables(gtab);
   // The segment table starts empty: lane sl will hold the stream's pair number n with n mod 16 = sl.
-  cols1_stream<C>(b, tab, Cols1Seg{-1, 0, 0, 0, 0, 0, 0.f}, Cols1Queue{order + cbeg, count, qhead, 0xFu, qv}, out,
+  cols1_stream<C>(b, tab, Cols1Seg{-1, 0, 0, 0, 0}, Cols1Queue{order + cbeg, count, qhead, 0xFu, qv}, out,
                   rescue_list, rescue_count, thr, use_rescue, fb_list, fb_count);
 }
 

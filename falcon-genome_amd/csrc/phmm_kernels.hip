@@ -693,14 +693,15 @@ static int cols6_forced_waves() {
   }();
   return forced > 0 ? forced : 0;
 }
-// One round of the chip: CUs x 4 SIMDs x kCols6Waves workgroups of one wave.
-static int cols6_grid() {
+// One round of the chip: CUs x 4 SIMDs x `waves` (the class's cols6_waves)
+// workgroups of one wave.
+static int cols6_grid(int waves) {
   if (const int f = cols6_forced_waves()) return f;
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
     cus = 256;
-  return cus * 4 * kCols6Waves;
+  return cus * 4 * waves;
 }
 
 int launch_phmm_forward(const PhmmDevBatch& b, const int32_t* order, int64_t count, int max_hap_len,
@@ -768,7 +769,7 @@ int launch_phmm_forward(const PhmmDevBatch& b, const int32_t* order, int64_t cou
     }
     const ColsKernel ck = cols_kernel(c);
     if (ck == kColsQueue) {
-      const unsigned grid = (unsigned)cols6_grid();
+      const unsigned grid = (unsigned)cols6_grid(cols6_waves(cols_C(c)));
       auto launch = [&](auto kern) -> int {
         hipLaunchKernelGGL(kern, dim3(grid), dim3(64), (size_t)kCols6Lds, st, b, order, bounds, j, t.tf, out,
                            rescue_list, rescue_count, thr, use_rescue ? 1 : 0, fb_list, fb_count, qheads + c);
