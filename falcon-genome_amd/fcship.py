@@ -1144,3 +1144,61 @@ def jg_genotype(cohort_arrays, pos, n_alt, tables, min_qual: int, max_pl=None, d
         entry(C.addressof(c), C.addressof(st), C.addressof(m), C.addressof(o))
     arrays["pl"] = arrays["pl"][:int(arrays["n_pl"][0])]
     return arrays
+
+
+# ---------------------------------------------------------------- indel realignment (include/fcsir.h)
+IR_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "fcsir.h")
+FCSIR_READ_MAX, FCSIR_SEQ_MAX, FCSIR_OVERHANG, FCSIR_ORIG_MAX = 512, 4096, 99, 1 << 30
+FCSIR_STATUS_FIELD, FCSIR_STATUS_PAIRS = 1, 2
+
+
+class IrBatch(C.Structure):
+    _fields_ = [("n_bins", C.c_int64), ("n_seq", C.c_int64), ("n_reads", C.c_int64), ("n_seq_bytes", C.c_int64),
+                ("n_read_bytes", C.c_int64), ("seq", C.c_void_p), ("seq_off", C.c_void_p), ("bin_seq", C.c_void_p),
+                ("read", C.c_void_p), ("qual", C.c_void_p), ("read_off", C.c_void_p), ("bin_read", C.c_void_p),
+                ("orig", C.c_void_p)]
+
+
+_sig("fcsir_score", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
+_sig("fcsir_workspace_bytes", C.c_int64, [C.c_int64])
+_sig("fcsir_score_dev", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                  C.c_void_p, C.c_void_p])
+
+
+def ir_header_symbols() -> list[str]:
+    """Function names declared in include/fcsir.h."""
+    import re
+    txt = re.sub(r"/\*.*?\*/", "", open(IR_HEADER_PATH).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(fcsir_[a-z0-9_]+)\s*\(", txt)))
+
+
+_IR_DTYPES = (np.uint8, np.int64, np.int64, np.uint8, np.uint8, np.int64, np.int64, np.int32)
+
+
+def ir_batch(seq, seq_off, bin_seq, read, qual, read_off, bin_read, orig, **kw):
+    """(fcsir_batch over host arrays, the arrays in its dtypes, which the caller keeps alive); kw overrides the counts."""
+    a = tuple(np.ascontiguousarray(x, t) for x, t in zip((seq, seq_off, bin_seq, read, qual, read_off, bin_read, orig), _IR_DTYPES))
+    counts = dict(n_bins=len(a[2]) - 1, n_seq=len(a[1]) - 1, n_reads=len(a[5]) - 1, n_seq_bytes=len(a[0]), n_read_bytes=len(a[3]))
+    counts.update(kw)
+    b = IrBatch(counts["n_bins"], counts["n_seq"], counts["n_reads"], counts["n_seq_bytes"], counts["n_read_bytes"],
+                *(_ptr(x) for x in a))
+    return b, a
+
+
+def ir_pairs(bin_seq, bin_read) -> int:
+    return int(np.sum(np.diff(np.asarray(bin_seq, np.int64)) * np.diff(np.asarray(bin_read, np.int64))))
+
+
+def ir_score(arrays, max_pairs=None, device: int = 0, entry=None, **kw):
+    """fcsir_score: (best uint32[n_pairs], off int32[n_pairs]) for the arrays (seq, seq_off, bin_seq, read, qual,
+    read_off, bin_read, orig); entry: another function (batch, best, off) in its place."""
+    b, keep = ir_batch(*arrays, **kw)
+    room = ir_pairs(keep[2], keep[6]) if max_pairs is None else max_pairs
+    best, off = np.zeros(max(room, 0), np.uint32), np.zeros(max(room, 0), np.int32)
+    n = C.c_int64(-1)
+    if entry is None:
+        check(lib.fcsir_score(device, C.addressof(b), _ptr(best), _ptr(off), room, C.addressof(n)))
+    else:
+        entry(C.addressof(b), _ptr(best), _ptr(off))
+        n.value = room
+    return best[:n.value], off[:n.value]

@@ -196,6 +196,8 @@ void BamRecord::set_aux_string(const char tag[2], const std::string& v) {
   aux += '\0';
 }
 
+void BamRecord::remove_aux(const char tag[2]) { erase_aux(aux, tag); }
+
 void BamRecord::set_aux_int(const char tag[2], int32_t v) {
   erase_aux(aux, tag);
   aux += tag[0];

@@ -45,6 +45,7 @@ struct BamRecord {
   bool get_aux_int(const char tag[2], int64_t& out) const;
   void set_aux_string(const char tag[2], const std::string& v);
   void set_aux_int(const char tag[2], int32_t v);
+  void remove_aux(const char tag[2]);  // nothing happens without the tag
 };
 
 struct BamHeader {

@@ -76,11 +76,9 @@ BqGenome load_genome(const std::string& fasta, const BamHeader& h) {
 
 // CHROM, POS and REF of every record of a plain or bgzipped VCF: the bits POS-1 .. POS-1+len(REF)-1.
 void load_known_sites(const std::string& path, const BamHeader& h, BqGenome& g, BqsrStats& st) {
-  if (!is_regular_file(path)) throw fileNotFound(path);
   std::unordered_map<std::string, int> index;
   for (size_t k = 0; k < h.names.size(); ++k) index[h.names[k]] = (int)k;
-  auto take = [&](const std::string& line) {
-    if (line.empty() || line[0] == '#') return;
+  known_sites_lines(path, [&](const std::string& line) {
     const size_t t1 = line.find('\t');
     const size_t t2 = t1 == std::string::npos ? t1 : line.find('\t', t1 + 1);
     const size_t t3 = t2 == std::string::npos ? t2 : line.find('\t', t2 + 1);
@@ -102,18 +100,7 @@ void load_known_sites(const std::string& path, const BamHeader& h, BqGenome& g, 
     for (int64_t p = std::max<int64_t>(pos - 1, 0); p < pos - 1 + len && p < clen; ++p)
       g.known[(size_t)((g0 + p) >> 6)] |= (uint64_t)1 << ((g0 + p) & 63);
     ++st.known_sites;
-  };
-  std::string line;
-  if (is_bgzf_file(path)) {
-    BgzfReader in(path);
-    while (in.getline(line)) take(line);
-  } else {
-    std::ifstream in(path);
-    while (std::getline(in, line)) {
-      if (!line.empty() && line.back() == '\r') line.pop_back();
-      take(line);
-    }
-  }
+  });
 }
 
 // -L: the intervals by contig index, sorted; a record is kept when it overlaps one.
@@ -286,6 +273,24 @@ std::vector<std::string> header_rg_names(const BqsrJob& job) {
 }
 
 }  // namespace
+
+void known_sites_lines(const std::string& path, const std::function<void(const std::string&)>& take) {
+  if (!is_regular_file(path)) throw fileNotFound(path);
+  auto data = [&](const std::string& line) {
+    if (!line.empty() && line[0] != '#') take(line);
+  };
+  std::string line;
+  if (is_bgzf_file(path)) {
+    BgzfReader in(path);
+    while (in.getline(line)) data(line);
+  } else {
+    std::ifstream in(path);
+    while (std::getline(in, line)) {
+      if (!line.empty() && line.back() == '\r') line.pop_back();
+      data(line);
+    }
+  }
+}
 
 bool gpu_bqsr_available() {
   const BqApi& a = bq_api();

@@ -4,6 +4,7 @@
 #pragma once
 
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -28,6 +29,9 @@ struct BqsrStats {
 
 // The loaded libfcship has the fcsbq_* entry points (the tests' CPU mock has not).
 bool gpu_bqsr_available();
+
+// The known-sites reader: the data lines of a plain or bgzipped VCF, one call each (also indel_run.cpp's -K).
+void known_sites_lines(const std::string& path, const std::function<void(const std::string&)>& take);
 
 BqsrStats baserecal_run(const BqsrJob& job);   // input -> report
 BqsrStats printreads_run(const BqsrJob& job);  // report + input -> output

@@ -23,6 +23,7 @@
 #include "gpu_seed.h"
 #include "seedext.h"
 #include "aligner.h"
+#include "indel.h"
 #include "intervals.h"
 #include "joint.h"
 #include "markdup.h"
@@ -639,6 +640,105 @@ int fcsg_jg_tables(double heterozygosity, double stand_call_conf, int n_samples,
 
 int fcsg_jg_genotype(const fcsjg_cohort* c, const fcsjg_sites* s, const fcsjg_model* m, int threads, const fcsjg_out* out) {
   return guard([&] { joint_genotype_host(*c, *s, *m, threads, *out); });
+}
+
+// The host statement of indel realignment (indel.h).  fcsg_ir_score is the
+// scoring step's oracle over the arguments of fcsir_score (include/fcsir.h).
+// fcsg_ir_targets merges n events (ref, start, end) and writes the targets back
+// in place; the number kept is returned.  fcsg_ir_left_align moves the indel
+// (a, k) of a one-indel alignment at ref[at]; ins_bases (k codes) rotate in
+// place; the new a is returned.  fcsg_ir_clean runs clean(bin) with the host
+// scores on a bin given as flat arrays: the window [lo, lo + n_ref) of codes,
+// n reads (start, duplicate, CIGAR words and codes / qualities by offsets),
+// n_known known indels (pos, k, ins, codes by offsets); the updates come back as
+// up_read / up_start / up_nm and CIGAR words by up_cigar_off (at most max_cigar
+// words), with the consensus count, the alt read count and the pick in info[3].
+int fcsg_ir_score(const fcsir_batch* b, int threads, uint32_t* best, int32_t* off) {
+  return guard([&] { ir_score_host(*b, threads, best, off); });
+}
+
+int fcsg_ir_targets(int32_t* ref, int64_t* start, int64_t* end, int n) {
+  int kept = 0;
+  const int g = guard([&] {
+    std::vector<IrInterval> ev;
+    for (int k = 0; k < n; ++k) ev.push_back({ref[k], start[k], end[k]});
+    const std::vector<IrInterval> t = ir_merge_targets(std::move(ev));
+    for (size_t k = 0; k < t.size(); ++k) ref[k] = t[k].ref, start[k] = t[k].start, end[k] = t[k].end;
+    kept = (int)t.size();
+  });
+  return g ? g : kept;
+}
+
+int fcsg_ir_cigar_events(int32_t ref, int64_t pos, const uint32_t* cigar, int n_cigar, int64_t* start, int64_t* end, int cap) {
+  int n = 0;
+  const int g = guard([&] {
+    std::vector<IrInterval> ev;
+    ir_cigar_events(ref, pos, std::vector<uint32_t>(cigar, cigar + n_cigar), ev);
+    if ((int)ev.size() > cap) throw failedCommand("[E::indel] more events than the caller has room for");
+    for (size_t k = 0; k < ev.size(); ++k) start[k] = ev[k].start, end[k] = ev[k].end;
+    n = (int)ev.size();
+  });
+  return g ? g : n;
+}
+
+int fcsg_ir_left_align(const uint8_t* ref, int64_t at, int a, int k, int ins, uint8_t* ins_bases) {
+  int out = 0;
+  const int g = guard([&] {
+    IrIndel d;
+    d.a = a, d.k = k, d.ins = ins != 0;
+    if (d.ins) d.bases.assign(ins_bases, ins_bases + k);
+    ir_left_align(ref, at, d);
+    if (d.ins) std::copy(d.bases.begin(), d.bases.end(), ins_bases);
+    out = d.a;
+  });
+  return g ? g : out;
+}
+
+int fcsg_ir_clean(int64_t lo, const uint8_t* ref, int64_t n_ref, int n, const int64_t* start, const uint8_t* duplicate,
+                  const uint32_t* cigar, const int64_t* cigar_off, const uint8_t* codes, const uint8_t* quals, const int64_t* base_off,
+                  int n_known, const int64_t* known_pos, const int32_t* known_k, const uint8_t* known_ins, const uint8_t* known_codes,
+                  const int64_t* known_off, int max_reads, int max_consensuses, int lod_tenths, int32_t* up_read, int64_t* up_start,
+                  int32_t* up_nm, uint32_t* up_cigar, int64_t* up_cigar_off, int64_t max_cigar, int64_t* info) {
+  int n_up = 0;
+  const int g = guard([&] {
+    IrBin bin;
+    bin.lo = lo, bin.hi = lo + n_ref, bin.ref.assign(ref, ref + n_ref);
+    for (int i = 0; i < n; ++i) {
+      IrRead r;
+      r.start = start[i], r.duplicate = duplicate[i] != 0;
+      r.cigar.assign(cigar + cigar_off[i], cigar + cigar_off[i + 1]);
+      r.codes.assign(codes + base_off[i], codes + base_off[i + 1]), r.quals.assign(quals + base_off[i], quals + base_off[i + 1]);
+      bin.reads.push_back(std::move(r));
+    }
+    for (int i = 0; i < n_known; ++i) {
+      IrKnown kn;
+      kn.pos = known_pos[i], kn.indel.k = known_k[i], kn.indel.ins = known_ins[i] != 0;
+      kn.indel.bases.assign(known_codes + known_off[i], known_codes + known_off[i + 1]);
+      bin.known.push_back(std::move(kn));
+    }
+    IrParams prm;
+    prm.max_reads = max_reads, prm.max_consensuses = max_consensuses, prm.lod_tenths = lod_tenths;
+    const IrPlan plan = ir_prepare(bin, prm);
+    info[0] = (int64_t)plan.cons.size(), info[1] = (int64_t)plan.alt.size(), info[2] = plan.skip;
+    std::vector<IrUpdate> ups;
+    if (!plan.skip && !plan.cons.empty() && !plan.alt.empty()) {
+      IrBatch batch;
+      batch.add(bin, plan);
+      std::vector<uint32_t> best((size_t)batch.pairs());
+      std::vector<int32_t> off((size_t)batch.pairs());
+      ir_score_host(batch.view(), 1, best.data(), off.data());
+      ups = ir_decide(bin, plan, prm, best.data(), off.data());
+    }
+    up_cigar_off[0] = 0;
+    for (size_t k = 0; k < ups.size(); ++k) {
+      up_read[k] = ups[k].read, up_start[k] = ups[k].start, up_nm[k] = ups[k].nm;
+      if (up_cigar_off[k] + (int64_t)ups[k].cigar.size() > max_cigar) throw failedCommand("[E::indel] more CIGAR words than the caller has room for");
+      std::copy(ups[k].cigar.begin(), ups[k].cigar.end(), up_cigar + up_cigar_off[k]);
+      up_cigar_off[k + 1] = up_cigar_off[k] + (int64_t)ups[k].cigar.size();
+    }
+    n_up = (int)ups.size();
+  });
+  return g ? g : n_up;
 }
 
 int fcsg_bam_index(const char* bam) {

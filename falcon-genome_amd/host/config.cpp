@@ -90,6 +90,12 @@ void Config::init(const std::string& root_dir) {
   declare("joint.heterozygosity", "0.001", "joint: the allele-count prior's heterozygosity");
   declare("joint.max_alt", "6", "joint: ALTs kept per site, the most named first (at most 6)");
   declare("joint.chunk_sites", "0", "joint: sites per genotyping call (0: as many as return 2^24 PLs at most)");
+  declare("indel.gpu", "false", "score (consensus, read) pairs on the GPU (fcsir_score) instead of on the host (indel)");
+  declare("indel.chunk_pairs", "1048576", "indel: (consensus, read) pairs per scoring call (a bin is never split)");
+  declare("indel.max_reads", "20000", "indel: a bin with more cleanable records is left untouched");
+  declare("indel.max_consensuses", "30", "indel: consensuses kept per bin, the first ones");
+  declare("indel.max_isize", "3000", "indel: a paired record with a larger |TLEN| is not realigned");
+  declare("indel.lod_tenths", "50", "indel: the least improvement of a bin's mismatch sum, in tenths (LOD 5.0)");
   // caller knobs (GATK HaplotypeCaller / Mutect2 argument defaults)
   declare("htc.min_base_quality", "10", "min base quality counted as evidence of activity");
   declare("htc.base_quality_threshold", "18", "PairHMM: base quals below this become 6");

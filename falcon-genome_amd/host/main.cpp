@@ -29,6 +29,7 @@
 #include "aligner.h"
 #include "bqsr_run.h"
 #include "depth_run.h"
+#include "indel_run.h"
 #include "joint_run.h"
 #include "ug_run.h"
 #include "intervals.h"
@@ -641,6 +642,48 @@ int joint_main(int argc, char** argv) {
   return 0;
 }
 
+// `fcs-genome indel | ir` (reference src/worker-indel.cpp, src/workers/IndelWorker.cpp
+// and RTCWorker.cpp, which run GATK 3's RealignerTargetCreator and IndelRealigner
+// per contig part): the sorted BAM streams three times through host/indel_run.h;
+// every (consensus, alt read) pair of every target is scored on the GPU
+// (indel.gpu=true, include/fcsir.h) or on the host.  With indel.gpu=false the
+// command needs no GPU.
+int indel_main(int argc, char** argv) {
+  Args a;
+  common_opts(a);
+  a.add("ref", "r", false, true, "reference genome path");
+  a.add("input", "i", false, true, "input BAM file or dir (coordinate-sorted)");
+  a.add("output", "o", false, true, "output BAM file (a .bai is written beside it)");
+  a.add("intervalList", "L", false, false, "interval list file: only the targets overlapping it are realigned");
+  a.add("known", "K", false, false, "known indels for realignment (VCF or VCF.gz; may repeat)");
+  a.add("merge-bam", "m", true, false, "accepted; the output is always one BAM");
+  a.add("sample-id", "", false, false, "sample tag for log files");
+  a.add("targets-out", "", false, false, "also write the realignment targets, in GATK's interval format");
+  try {
+    a.parse(argc, argv);
+  } catch (helpRequest&) {
+    std::cerr << "'fcs-genome indel' options:\n" << a.help();
+    throw;
+  }
+  IndelJob job;
+  job.ref = a.get("ref"), job.input = a.get("input"), job.output = a.get("output");
+  if (a.has("intervalList")) job.intervals = a.get("intervalList");
+  if (a.has("sample-id")) (void)a.get("sample-id");
+  if (a.has("targets-out")) job.targets_out = a.get("targets-out");
+  job.known = a.all("known");
+  require_path(job.ref), require_path(job.input, true);
+  if (!job.intervals.empty()) require_path(job.intervals);
+  for (const std::string& k : job.known) require_path(k);
+  refuse_existing(a, job.targets_out.empty() ? std::vector<std::string>{job.output} : std::vector<std::string>{job.output, job.targets_out});
+  if (conf().get_bool("indel.gpu")) job.device = slots().front();
+  const IndelRunStats st = indel_run(job);
+  std::cerr << "[fcs-genome indel] " << st.records << " records, " << st.known << " known indels, " << st.targets << " targets, "
+            << st.bins << " bins (" << st.untouched << " left untouched), " << st.alt_reads << " alt reads, " << st.pairs
+            << " pairs, " << st.cleaned << " bins cleaned, " << st.realigned << " records realigned, " << st.mates << " mates fixed";
+  stats_tail(st.seconds, st.on_device);
+  return 0;
+}
+
 // `fcs-genome index -r ref.fasta`: the aligner's FMD-index, saved next to the
 // FASTA (<ref>.fcsidx) so that align maps it instead of building one per run
 // (bwa-flow reads the prebuilt bwa index; the reference expects it beside the
@@ -769,6 +812,7 @@ int print_help() {
                "Usage: fcs-genome [command] <options>\n\nCommands:\n"
                "  align           align FASTQ reads into a sorted BAM (GPU banded SW)\n"
                "  markdup         mark duplicate reads of a BAM (GPU sort + segmented arg-max)\n"
+               "  indel           indel realignment of a BAM, IndelRealigner-style (GPU consensus scoring)\n"
                "  baserecal       base recalibration table of a BAM against known sites (GPU covariate counting)\n"
                "  printreads      apply a base recalibration table to a BAM (GPU table lookup)\n"
                "  bqsr            baserecal and printreads in one run\n"
@@ -821,6 +865,7 @@ int main(int argc, char** argv) {
     else if (cmd == "depth") ret = depth_main(argc - 1, argv + 1);
     else if (cmd == "ug" || cmd == "unifiedgeno") ret = ug_main(argc - 1, argv + 1);
     else if (cmd == "joint") ret = joint_main(argc - 1, argv + 1);
+    else if (cmd == "indel" || cmd == "ir") ret = indel_main(argc - 1, argv + 1);
     else if (cmd == "synth") ret = synth_main(argc - 1, argv + 1);
     else if (cmd == "index") ret = index_main(argc - 1, argv + 1);
     else if (cmd == "conf") {
