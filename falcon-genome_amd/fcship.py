@@ -1202,3 +1202,95 @@ def ir_score(arrays, max_pairs=None, device: int = 0, entry=None, **kw):
         entry(C.addressof(b), _ptr(best), _ptr(off))
         n.value = room
     return best[:n.value], off[:n.value]
+
+
+# ---------------------------------------------------------------- the callers' pileup (include/fcspu.h)
+PU_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "fcspu.h")
+FCSPU_TILE, FCSPU_WINDOW_MAX, FCSPU_TABLE_ROWS, FCSPU_BATCHES_MAX = 256, 1 << 24, 94, 2
+(FCSPU_STATUS_FIELD, FCSPU_STATUS_REF, FCSPU_STATUS_ORDER, FCSPU_STATUS_SITES, FCSPU_STATUS_SNVS,
+ FCSPU_STATUS_LETTER) = 1, 2, 4, 8, 16, 32
+
+
+class PuParams(C.Structure):
+    _fields_ = [("min_bq", C.c_int32), ("want_gl", C.c_int32), ("frac", C.c_double)]
+
+
+class PuOut(C.Structure):
+    _fields_ = [("depth", C.c_void_p), ("events", C.c_void_p), ("gl", C.c_void_p), ("sites", C.c_void_p),
+                ("max_sites", C.c_int64), ("n_sites", C.c_void_p), ("snvs", C.c_void_p), ("max_snvs", C.c_int64),
+                ("n_snvs", C.c_void_p)]
+
+
+PU_SNV = np.dtype([("offset", np.int32), ("alt", np.uint8), ("reserved", np.uint8, 3), ("count", np.int32)])
+assert PU_SNV.itemsize == 12
+
+_sig("fcspu_pile", C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_void_p])
+_sig("fcspu_workspace_bytes", C.c_int64, [C.c_void_p, C.c_int32, C.c_int64])
+_sig("fcspu_pile_dev", C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])
+
+
+def pu_header_symbols() -> list[str]:
+    """Function names declared in include/fcspu.h (fcspu_table is libfcsgenome's)."""
+    import re
+    txt = re.sub(r"/\*.*?\*/", "", open(PU_HEADER_PATH).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(fcspu_[a-z0-9_]+)\s*\(", txt)))
+
+
+def pu_table():
+    """fcspu_table: the callers' reference model T[94][3] as float64, from libfcsgenome.so (host only)."""
+    host = C.CDLL(os.path.join(HERE, "libfcsgenome.so"))
+    t = np.zeros((FCSPU_TABLE_ROWS, 3), np.float64)
+    if host.fcspu_table(C.c_void_p(t.ctypes.data)) != 0:
+        raise RuntimeError("fcspu_table failed")
+    return t
+
+
+def pu_workspace_bytes(n_records, length) -> int:
+    n = np.ascontiguousarray(n_records, np.int64)
+    return int(lib.fcspu_workspace_bytes(n.ctypes.data, len(n), length))
+
+
+def pu_out(length, want_gl=True, max_sites=None, max_snvs=None):
+    """(fcspu_out over fresh host arrays, the arrays by name, which the caller keeps alive)."""
+    max_sites = length if max_sites is None else max_sites
+    max_snvs = 4 * length if max_snvs is None else max_snvs
+    a = dict(depth=np.full(length, -1, np.int32), events=np.full(length, -1, np.int32),
+             gl=np.full(3 * length if want_gl else 0, np.nan, np.float64), sites=np.full(max(max_sites, 1), -1, np.int32),
+             snvs=np.zeros(max(max_snvs, 1), PU_SNV), n_sites=np.full(1, -7, np.int64), n_snvs=np.full(1, -7, np.int64))
+    o = PuOut(_ptr(a["depth"]), _ptr(a["events"]), _ptr(a["gl"]), a["sites"].ctypes.data, max_sites, a["n_sites"].ctypes.data,
+              a["snvs"].ctypes.data, max_snvs, a["n_snvs"].ctypes.data)
+    return o, a
+
+
+def pu_pile(batches, window, ref, table, min_bq: int = 10, frac: float = 0.15, want_gl: bool = True, events_in=None,
+            max_sites=None, max_snvs=None, device: int = 0, entry=None, kw=None, clock=None):
+    """fcspu_pile over one or two batches (ug_arrays' argument tuples) and window = (ref_id, start, len, contig_len);
+    ref: the window's len ASCII reference bytes.  Returns dict(depth, events, gl[len][3] or None, sites, snvs (PU_SNV)).
+    entry: another function (batches, n, params, window, ref, events_in, out) in its place (the host statement);
+    kw: per batch, ug_batch's count overrides; clock: a dict that takes the seconds spent inside the entry."""
+    import time
+    keep = [ug_arrays(*b) for b in batches]
+    kw = kw or [{}] * len(keep)
+    arr = (UgBatch * len(keep))(*[ug_batch(a, **k) for a, k in zip(keep, kw)])
+    ref_id, start, length, contig_len = window
+    w = UgWindow(ref_id, 0, start, length, contig_len)
+    prm = PuParams(min_bq, int(want_gl), frac)
+    ref = np.frombuffer(ref.encode() if isinstance(ref, str) else bytes(ref), np.uint8)
+    assert len(ref) == length
+    table = np.ascontiguousarray(table, np.float64)
+    ev = None if events_in is None else np.ascontiguousarray(events_in, np.int32)
+    o, a = pu_out(length, want_gl, max_sites, max_snvs)
+    evp = 0 if ev is None else ev.ctypes.data
+    t0 = time.perf_counter()
+    if entry is None:
+        check(lib.fcspu_pile(device, C.addressof(arr), len(keep), C.addressof(prm), C.addressof(w), _ptr(ref), table.ctypes.data,
+                             evp, C.addressof(o)))
+    else:
+        entry(C.addressof(arr), len(keep), C.addressof(prm), C.addressof(w), _ptr(ref), evp, C.addressof(o))
+    if clock is not None:
+        clock["seconds"] = time.perf_counter() - t0
+    ns, nv = int(a["n_sites"][0]), int(a["n_snvs"][0])
+    return dict(depth=a["depth"], events=a["events"], gl=a["gl"].reshape(length, 3) if want_gl else None,
+                sites=a["sites"][:ns].copy(), snvs=a["snvs"][:nv].copy())

@@ -25,7 +25,9 @@
 #include "common.h"
 #include "fcship.h"
 #include "gatk_prep.h"
+#include "flat_batch.h"
 #include "hugebuf.h"
+#include "pileup.h"
 
 namespace fcsg {
 
@@ -48,6 +50,10 @@ void CallerStats::add(const CallerStats& o) {
   rescue_device_seconds += o.rescue_device_seconds;
   decode_seconds += o.decode_seconds;
   pileup_seconds += o.pileup_seconds;
+  pileup_gpu_chunks += o.pileup_gpu_chunks;
+  pileup_host_chunks += o.pileup_host_chunks;
+  pileup_device_seconds += o.pileup_device_seconds;
+  pileup_flatten_seconds += o.pileup_flatten_seconds;
   region_seconds += o.region_seconds;
   genotype_seconds += o.genotype_seconds;
   output_seconds += o.output_seconds;
@@ -57,29 +63,6 @@ void CallerStats::add(const CallerStats& o) {
 }
 
 namespace {
-
-// A read of the window: its CIGAR, bases, qualities and BI / BD strings live
-// in the window's HugeSlab (no per-read heap blocks).
-template <typename T>
-struct View {
-  const T* p = nullptr;
-  size_t n = 0;
-  const T* begin() const { return p; }
-  const T* end() const { return p + n; }
-  size_t size() const { return n; }
-  bool empty() const { return n == 0; }
-  const T& operator[](size_t i) const { return p[i]; }
-};
-struct Read {
-  int32_t pos = 0;
-  int64_t end = 0;
-  View<uint32_t> cigar;
-  std::string_view seq;
-  View<uint8_t> qual;
-  int mapq = 0;
-  std::string_view bi, bd;
-};
-static_assert(std::is_trivially_copyable_v<Read>, "Read lives in a HugeVec");
 
 // window chunks of this thread inflated on the GPU / on the host (gpu.bam_inflate)
 thread_local int64_t tl_inflate_gpu = 0, tl_inflate_host = 0;
@@ -175,157 +158,6 @@ void load_reads(const std::vector<std::string>& bams, const std::string& chrom, 
   for (const std::string& b : bams) load_reads_one(b, chrom, beg, end, opt, slab, out);
   if (bams.size() > 1)
     std::stable_sort(out.begin(), out.end(), [](const Read& a, const Read& b) { return a.pos < b.pos; });
-}
-
-struct Allele {
-  int64_t pos;  // 0-based anchor
-  std::string ref, alt;
-  bool operator<(const Allele& o) const { return std::tie(pos, ref, alt) < std::tie(o.pos, o.ref, o.alt); }
-  int64_t ref_end() const { return pos + (int64_t)ref.size(); }
-};
-
-struct Pileup {
-  int64_t wb = 0;
-  HugeArray<int> depth, events;
-  // allele events of the reads — SNVs as packed (pos, ref, alt) keys, indels
-  // as Alleles — then (finish_support) sorted and counted: the support of
-  // each distinct allele in (pos, ref, alt) order
-  HugeVec<uint64_t> snv_events;
-  std::vector<Allele> indel_events;
-  std::vector<std::pair<Allele, int>> support;
-  // GVCF reference model: per position, sum over bases of log10 P(base | 0/0,
-  // 0/1, 1/1) with 1 = <NON_REF> (any other base)
-  HugeArray<double> gl;  // 3 per position; empty unless GVCF
-};
-
-// log10 P(base | genotype) per base quality: [q][0] ref base under 0/0 (1 - e),
-// [q][1] any base under 0/1 (0.5 (1 - e) + 0.5 e / 3), [q][2] non-ref base
-// under 0/0 (e / 3); a ref base under 1/1 is e / 3, a non-ref base 1 - e.
-struct RefModel {
-  double t[94][3];
-  RefModel() {
-    for (int q = 0; q < 94; ++q) {
-      const double e = std::min(0.75, std::pow(10.0, -q / 10.0));
-      t[q][0] = std::log10(1.0 - e);
-      t[q][1] = std::log10(0.5 * (1.0 - e) + 0.5 * e / 3.0);
-      t[q][2] = std::log10(e / 3.0);
-    }
-  }
-};
-const RefModel& ref_model() {
-  static const RefModel m;
-  return m;
-}
-
-inline uint64_t snv_key(int64_t pos, char ref, char alt) {
-  return ((uint64_t)pos << 16) | ((uint64_t)(uint8_t)ref << 8) | (uint8_t)alt;
-}
-
-// Walks every read's CIGAR once: depth, mismatch/indel events and allele support.
-void build_pileup(const std::string& ref, const HugeVec<Read>& reads, int min_bq, Pileup& pu) {
-  const int64_t n = (int64_t)pu.depth.size();
-  const int64_t wb = pu.wb, we = pu.wb + n;
-  auto in = [&](int64_t p) { return p >= wb && p < we; };
-  const RefModel& M = ref_model();
-  int* depth = pu.depth.data();
-  int* events = pu.events.data();
-  double* gl = pu.gl.empty() ? nullptr : pu.gl.data();
-  for (const Read& rd : reads) {
-    int64_t rp = rd.pos;
-    size_t q = 0;
-    for (uint32_t c : rd.cigar) {
-      const uint32_t len = cigar_len(c);
-      switch (cigar_op(c)) {
-        case kM: case kEq: case kX: {
-          // only the bases inside the window
-          const int64_t lo = std::max<int64_t>(rp, wb), hi = std::min<int64_t>(rp + len, we);
-          for (int64_t p = lo; p < hi; ++p) {
-            const size_t qi = q + (size_t)(p - rp);
-            const uint8_t bq = rd.qual[qi];
-            if (bq < min_bq) continue;
-            ++depth[p - wb];
-            const char b = rd.seq[qi], r = ref[p];
-            const bool nonref = b != r && r != 'N' && b != 'N';
-            if (nonref) {
-              ++events[p - wb];
-              pu.snv_events.emplace_back() = snv_key(p, r, b);
-            }
-            if (gl) {
-              const double* t = M.t[std::min<int>(bq, 93)];
-              double* g = gl + 3 * (p - wb);
-              g[0] += t[nonref ? 2 : 0];
-              g[1] += t[1];
-              g[2] += t[nonref ? 0 : 2];
-            }
-          }
-          rp += len;
-          q += len;
-          break;
-        }
-        case kI:
-          if (rp > rd.pos && in(rp - 1)) {
-            ++events[rp - 1 - wb];
-            pu.indel_events.push_back({rp - 1, std::string(1, ref[rp - 1]), std::string(1, ref[rp - 1]).append(rd.seq.substr(q, len))});
-          }
-          q += len;
-          break;
-        case kD:
-          if (rp > rd.pos && in(rp - 1) && rp + len <= (int64_t)ref.size()) {
-            ++events[rp - 1 - wb];
-            pu.indel_events.push_back({rp - 1, ref.substr(rp - 1, len + 1), std::string(1, ref[rp - 1])});
-          }
-          for (int64_t p = std::max<int64_t>(rp, wb), hi = std::min<int64_t>(rp + len, we); p < hi; ++p) ++depth[p - wb];
-          rp += len;
-          break;
-        case kN: rp += len; break;
-        case kS: q += len; break;
-        default: break;
-      }
-    }
-  }
-}
-
-// The distinct alleles of the pileup's events seen in at least two reads
-// (the least support a candidate allele needs), with their read counts, in
-// (pos, ref, alt) order: the SNV keys sort as integers (a one-base REF and
-// ALT compare as their bytes), the indels as Alleles, and the two runs merge
-// (an indel never equals an SNV: its REF or ALT is longer than one base).
-void finish_support(Pileup& pu) {
-  std::sort(pu.snv_events.begin(), pu.snv_events.end());
-  std::sort(pu.indel_events.begin(), pu.indel_events.end());
-  pu.support.clear();
-  size_t i = 0, j = 0;
-  const size_t ns = pu.snv_events.size(), ni = pu.indel_events.size();
-  auto next_snv = [&] {  // skip SNVs seen once
-    while (i < ns && (i + 1 >= ns || pu.snv_events[i + 1] != pu.snv_events[i])) ++i;
-  };
-  auto next_indel = [&] {
-    while (j < ni && (j + 1 >= ni || pu.indel_events[j] < pu.indel_events[j + 1])) ++j;
-  };
-  next_snv();
-  next_indel();
-  while (i < ns || j < ni) {
-    if (i < ns) {
-      const uint64_t k = pu.snv_events[i];
-      Allele a{(int64_t)(k >> 16), std::string(1, (char)((k >> 8) & 0xff)), std::string(1, (char)(k & 0xff))};
-      if (j >= ni || a < pu.indel_events[j]) {
-        size_t e = i;
-        while (e < ns && pu.snv_events[e] == k) ++e;
-        pu.support.emplace_back(std::move(a), (int)(e - i));
-        i = e;
-        next_snv();
-        continue;
-      }
-    }
-    Allele& a = pu.indel_events[j];
-    size_t e = j + 1;
-    while (e < ni && !(a < pu.indel_events[e])) ++e;
-    pu.support.emplace_back(std::move(a), (int)(e - j));
-    j = e;
-    next_indel();
-  }
-  pu.snv_events = HugeVec<uint64_t>();
-  std::vector<Allele>().swap(pu.indel_events);
 }
 
 // Query slice [qs, qe) of the read whose bases align inside [rb, re) (inserted
@@ -906,6 +738,11 @@ CallerStats call_intervals(const Reference& ref, const std::vector<std::string>&
                            const CallerOptions& opt, VcfWriter& out) {
   CallerStats st;
   const CombinerScope combiner(opt);
+  const int pile_device =
+      opt.gpu_pileup ? device_or_host(opt.gpu, gpu_pileup_available(),
+                                      "[fcs-genome] htc.gpu_pileup: the loaded libfcship has no fcspu_pile entry point; "
+                                      "windows are piled up on the host\n")
+                     : -1;
   const uint64_t t0 = now_us();
   const double cpu0 = thread_cpu();
   std::FILE* dump = opt.dump_path.empty() ? nullptr : std::fopen(opt.dump_path.c_str(), "ab");
@@ -986,18 +823,24 @@ CallerStats call_intervals(const Reference& ref, const std::vector<std::string>&
       pu.depth = HugeArray<int>((size_t)(we - wb));  // zero-filled
       pu.events = HugeArray<int>((size_t)(we - wb));
       if (opt.gvcf && !opt.somatic) pu.gl = HugeArray<double>(3 * (size_t)(we - wb));
-      build_pileup(seq, reads[0], opt.min_base_quality, pu);
       // activity: the sample's evidence, or in Mutect2 mode the tumor's alone
       // (Mutect2's activity profile is a tumor-evidence test; over tumor +
       // normal depth a somatic allele at the tumor's fraction reads as half
       // of it and its site is missed)
       std::vector<int64_t> sites;
       const double frac = opt.somatic ? opt.somatic_active_fraction : opt.active_fraction;
-      for (int64_t p = wb; p < we; ++p) {
-        const int ev = pu.events[p - wb], dp = std::max(1, pu.depth[p - wb]);
-        if (ev >= 2 && ev >= frac * dp) sites.push_back(p);
+      if (pile_device >= 0) {
+        // htc.gpu_pileup: the per-base part in chunks on the device, the per-op part here
+        PileupRunStats ps;
+        pileup_window_device(pile_device, opt.pileup_chunk_bp, seq, ci, reads, opt.somatic ? 2 : 1, opt.min_base_quality, frac,
+                             pu, sites, ps, opt.somatic ? "mutect2" : "htc");
+        st.pileup_gpu_chunks += ps.gpu_chunks, st.pileup_host_chunks += ps.host_chunks;
+        st.pileup_device_seconds += ps.device_seconds, st.pileup_flatten_seconds += ps.flatten_seconds;
+      } else {
+        build_pileup(seq, reads[0].data(), reads[0].size(), opt.min_base_quality, pu);
+        active_sites(pu, wb, we, frac, sites);
+        if (opt.somatic) build_pileup(seq, reads[1].data(), reads[1].size(), opt.min_base_quality, pu);
       }
-      if (opt.somatic) build_pileup(seq, reads[1], opt.min_base_quality, pu);
       finish_support(pu);
       clusters.clear();
       bool grow_l = false, grow_r = false;

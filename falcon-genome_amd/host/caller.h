@@ -50,6 +50,10 @@ struct CallerOptions {
   // window BAM blocks through fcs_bgzf_inflate (BgzfReader::use_device); off by
   // default: at the htc shard shape the host's libdeflate is faster
   bool gpu_inflate = false;
+  // htc.gpu_pileup: the per-base part of a window's pileup through fcspu_pile
+  // (pileup.h), pileup_chunk_bp loci per call; off by default
+  bool gpu_pileup = false;
+  int64_t pileup_chunk_bp = 1048576;
   // called before each PairHMM pass until it returns false: while the device
   // is still coming up it runs another queued shard on this thread
   // (gpu.warmup_help; set by the shard workers, empty elsewhere)
@@ -75,6 +79,11 @@ struct CallerStats {
   int64_t faults[4] = {0, 0, 0, 0};
   // device time of the PairHMM calls (HIP events: schedule + forward + rescue) and of the fp64 rescue alone
   double phmm_device_seconds = 0, rescue_device_seconds = 0;
+  // htc.gpu_pileup: a window's chunks piled up by the device / sent down the
+  // host path (a read letter the device does not count), and the wall times
+  // inside fcspu_pile and of the flatten copy, both part of pileup_seconds
+  int64_t pileup_gpu_chunks = 0, pileup_host_chunks = 0;
+  double pileup_device_seconds = 0, pileup_flatten_seconds = 0;  // the latter: the reads copied into the flat batch
   // other shards run on this thread while the device came up (help_while_cold):
   // their wall and CPU time, left out of this shard's figures above
   int64_t helped_tasks = 0;

@@ -27,6 +27,7 @@
 #include "intervals.h"
 #include "joint.h"
 #include "markdup.h"
+#include "pileup.h"
 #include "sample_sheet.h"
 #include "vcf.h"
 
@@ -640,6 +641,22 @@ int fcsg_jg_tables(double heterozygosity, double stand_call_conf, int n_samples,
 
 int fcsg_jg_genotype(const fcsjg_cohort* c, const fcsjg_sites* s, const fcsjg_model* m, int threads, const fcsjg_out* out) {
   return guard([&] { joint_genotype_host(*c, *s, *m, threads, *out); });
+}
+
+// The host statement of the callers' pileup (pileup.h) over the arguments of
+// fcspu_pile (include/fcspu.h), and the reference model's table, which is the
+// one the caller hands the device.
+int fcsg_pu_pile(const fcspu_batch* batches, int n_batches, const fcspu_params* prm, const fcspu_window* w, const uint8_t* ref,
+                 const int32_t* events_in, const fcspu_out* out) {
+  return guard([&] { pileup_host(batches, n_batches, *prm, *w, ref, events_in, *out); });
+}
+
+int fcsg_pu_op_events(const fcspu_batch* batch, const fcspu_window* w, const char* contig, int32_t* events) {
+  return guard([&] { pileup_ops_host(*batch, *w, std::string(contig, (size_t)w->contig_len), events); });
+}
+
+int fcspu_table(double* table) {
+  return guard([&] { std::memcpy(table, &ref_model().t[0][0], sizeof(double) * 3 * FCSPU_TABLE_ROWS); });
 }
 
 // The host statement of indel realignment (indel.h).  fcsg_ir_score is the

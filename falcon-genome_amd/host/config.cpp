@@ -104,6 +104,9 @@ void Config::init(const std::string& root_dir) {
   declare("htc.min_mapq", "20", "reads below this mapping quality are ignored");
   declare("htc.active_fraction", "0.15", "mismatch/indel fraction that makes a site active");
   declare("mutect2.active_fraction", "0.10", "tumor mismatch/indel fraction that makes a site active (mutect2)");
+  declare("htc.gpu_pileup", "false",
+          "pile a calling window's aligned bases up on the GPU (fcspu_pile) instead of on the shard's host thread (htc, mutect2)");
+  declare("htc.pileup_chunk_bp", "1048576", "loci per fcspu_pile call with htc.gpu_pileup (DESIGN 4.15)");
   declare("htc.padding", "50", "bases added either side of an active site");
   declare("htc.max_region", "300", "max active region length");
   declare("htc.max_reads_per_region", "250", "downsampling cap per region");

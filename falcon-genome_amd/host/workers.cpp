@@ -46,6 +46,9 @@ CallerOptions caller_options_from_config(int gpu) {
   o.combine_ms = c.get_int("gpu.phmm.combine_ms");
   o.fp64_rescue = c.get_bool("gpu.phmm.rescue");
   o.gpu_inflate = c.get_bool("gpu.bam_inflate");
+  o.gpu_pileup = c.get_bool("htc.gpu_pileup");
+  o.pileup_chunk_bp = c.get_int("htc.pileup_chunk_bp");
+  if (o.pileup_chunk_bp < 1) throw invalidParam("htc.pileup_chunk_bp");
   // (merged passes wait for every active shard's pass: a shard run inside
   // another's flush would hold that pass back, so no help then)
   if (c.get_bool("gpu.warmup_help") && o.combine_ms == 0)
@@ -124,6 +127,10 @@ int HTCWorker::run(TaskContext& ctx) {
                  stats_.region_seconds, stats_.genotype_seconds, stats_.output_seconds, stats_.cpu_seconds,
                  (long long)stats_.faults[0], (long long)stats_.faults[1], (long long)stats_.faults[2],
                  (long long)stats_.faults[3], (long long)stats_.helped_tasks, stats_.helped_seconds);
+  if (ctx.log && opt.gpu_pileup)
+    std::fprintf(ctx.log, "[fcs-genome %s] shard %d pileup: %lld gpu chunks, %lld host chunks, device %.4f s, flatten %.4f s\n", "htc", contig_,
+                 (long long)stats_.pileup_gpu_chunks, (long long)stats_.pileup_host_chunks, stats_.pileup_device_seconds,
+                 stats_.pileup_flatten_seconds);
   return 0;
 }
 
@@ -178,6 +185,10 @@ int Mutect2Worker::run(TaskContext& ctx) {
                  stats_.region_seconds, stats_.genotype_seconds, stats_.output_seconds, stats_.cpu_seconds,
                  (long long)stats_.faults[0], (long long)stats_.faults[1], (long long)stats_.faults[2],
                  (long long)stats_.faults[3]);
+  if (ctx.log && opt.gpu_pileup)
+    std::fprintf(ctx.log, "[fcs-genome %s] shard %d pileup: %lld gpu chunks, %lld host chunks, device %.4f s, flatten %.4f s\n", "mutect2", contig_,
+                 (long long)stats_.pileup_gpu_chunks, (long long)stats_.pileup_host_chunks, stats_.pileup_device_seconds,
+                 stats_.pileup_flatten_seconds);
   return 0;
 }
 
