@@ -1294,3 +1294,51 @@ def pu_pile(batches, window, ref, table, min_bq: int = 10, frac: float = 0.15, w
     ns, nv = int(a["n_sites"][0]), int(a["n_snvs"][0])
     return dict(depth=a["depth"], events=a["events"], gl=a["gl"].reshape(length, 3) if want_gl else None,
                 sites=a["sites"][:ns].copy(), snvs=a["snvs"][:nv].copy())
+
+
+# ---------------------------------------------------------------- minimizer chaining (include/fcsmm.h)
+MM_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "fcsmm.h")
+FCSMM_LOOKBACK, FCSMM_SPAN_MAX, FCSMM_GAP_MAX, FCSMM_READ_ANCHORS = 64, 64, 1 << 20, 1 << 24
+FCSMM_STATUS_FIELD, FCSMM_STATUS_ORDER = 1, 2
+
+
+class MmBatch(C.Structure):
+    _fields_ = [("n_reads", C.c_int64), ("n_anchors", C.c_int64), ("t", C.c_void_p), ("q", C.c_void_p),
+                ("read_off", C.c_void_p), ("max_gap", C.c_int32), ("bw", C.c_int32), ("span", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+_sig("fcsmm_chain", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
+_sig("fcsmm_workspace_bytes", C.c_int64, [C.c_int64, C.c_int64])
+_sig("fcsmm_chain_dev", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])
+
+
+def mm_header_functions() -> list[str]:
+    """Function names declared in include/fcsmm.h."""
+    import re
+    txt = re.sub(r"/\*.*?\*/", "", open(MM_HEADER_PATH).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(fcsmm_[a-z0-9_]+)\s*\(", txt)))
+
+
+_MM_DTYPES = (np.int64, np.int32, np.int64)
+
+
+def mm_batch(t, q, read_off, max_gap: int = 100, bw: int = 50, span: int = 21, **kw):
+    """(fcsmm_batch over host arrays, the arrays in its dtypes, which the caller keeps alive); kw overrides the counts."""
+    a = tuple(np.ascontiguousarray(x, d) for x, d in zip((t, q, read_off), _MM_DTYPES))
+    counts = dict(n_reads=len(a[2]) - 1, n_anchors=len(a[0]))
+    counts.update(kw)
+    b = MmBatch(counts["n_reads"], counts["n_anchors"], *(_ptr(x) for x in a), max_gap, bw, span, 0)
+    return b, a
+
+
+def mm_chain(arrays, max_gap: int = 100, bw: int = 50, span: int = 21, device: int = 0, entry=None, fill=-7, **kw):
+    """fcsmm_chain: (f int32[n_anchors], p int32[n_anchors]) for the arrays (t, q, read_off); entries no read holds keep
+    `fill`.  entry: another function (batch, f, p) in its place (the host statement)."""
+    b, keep = mm_batch(*arrays, max_gap=max_gap, bw=bw, span=span, **kw)
+    f, p = np.full(len(keep[0]), fill, np.int32), np.full(len(keep[0]), fill, np.int32)
+    if entry is None:
+        check(lib.fcsmm_chain(device, C.addressof(b), _ptr(f), _ptr(p)))
+    else:
+        entry(C.addressof(b), _ptr(f), _ptr(p))
+    return f, p

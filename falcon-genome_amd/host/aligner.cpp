@@ -6,6 +6,7 @@
 #include <array>
 #include <cmath>
 #include <condition_variable>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <fstream>
@@ -17,6 +18,7 @@
 #include <set>
 #include <sstream>
 #include <thread>
+#include <tuple>
 #include <unordered_map>
 
 #include "common.h"
@@ -25,6 +27,8 @@
 #include "fcship.h"
 #include "intervals.h"
 #include "markdup.h"
+#include "gpu_chain.h"
+#include "mm_rules.h"
 #include "seedext.h"
 #include "workers.h"
 
@@ -157,6 +161,62 @@ SeedParams seed_params(const AlignOptions& opt) {
   return P;
 }
 
+// bwa mem_chain_weight (query bases covered by the seeds, min with the
+// reference's) and mem_chain_flt over the chains of one read (not empty); the
+// kept ones go to R.chains.  Shared by both seeders.
+void finish_chains(const AlignOptions& opt, ReadAln& R, std::vector<Chain>& chains) {
+  const int L = (int)R.code[0].size();
+  for (Chain& ch : chains) {  // bwa mem_chain_weight: query bases covered by the seeds (min with the reference's)
+    int64_t wq = 0, wr = 0, endq = 0, endr = 0;
+    for (const Seed& sd : ch.s) {
+      if (sd.qbeg >= endq) wq += sd.len;
+      else if (sd.qbeg + sd.len > endq) wq += sd.qbeg + sd.len - endq;
+      endq = std::max<int64_t>(endq, sd.qbeg + sd.len);
+    }
+    std::vector<const Seed*> byr;
+    for (const Seed& sd : ch.s) byr.push_back(&sd);
+    std::sort(byr.begin(), byr.end(), [](const Seed* a, const Seed* b) { return a->rbeg < b->rbeg; });
+    for (const Seed* sd : byr) {
+      if (sd->rbeg >= endr) wr += sd->len;
+      else if (sd->rbeg + sd->len > endr) wr += sd->rbeg + sd->len - endr;
+      endr = std::max<int64_t>(endr, sd->rbeg + sd->len);
+    }
+    ch.weight = (int)std::min(wq, wr);
+    const int b = ch.s.front().qbeg, e = ch.s.back().qbeg + ch.s.back().len;  // oriented
+    ch.qb = ch.rev ? L - e : b;
+    ch.qe = ch.rev ? L - b : e;
+  }
+  // ---- bwa mem_chain_flt
+  std::stable_sort(chains.begin(), chains.end(), [](const Chain& a, const Chain& b) { return a.weight > b.weight; });
+  std::vector<int> kept{0};
+  chains[0].kept = 3;
+  for (int i = 1; i < (int)chains.size(); ++i) {
+    bool large_ovlp = false;
+    size_t k = 0;
+    for (; k < kept.size(); ++k) {
+      Chain& cj = chains[kept[k]];
+      const Chain& ci = chains[i];
+      const int b_max = std::max(cj.qb, ci.qb), e_min = std::min(cj.qe, ci.qe);
+      if (e_min > b_max) {
+        const int li = ci.qe - ci.qb, lj = cj.qe - cj.qb, min_l = std::min(li, lj);
+        if (e_min - b_max >= min_l * opt.mask_level && min_l < opt.max_chain_gap) {
+          large_ovlp = true;
+          if (cj.first < 0) cj.first = i;
+          if (ci.weight < cj.weight * opt.drop_ratio && cj.weight - ci.weight >= opt.k << 1) break;
+        }
+      }
+    }
+    if (k == kept.size()) {
+      kept.push_back(i);
+      chains[i].kept = large_ovlp ? 2 : 3;
+    }
+  }
+  for (int j : kept)
+    if (chains[j].first >= 0) chains[chains[j].first].kept = 1;
+  for (Chain& ch : chains)
+    if (ch.kept > 0) R.chains.push_back(std::move(ch));
+}
+
 // Seeds and chains of one read (bwa mem_collect_intv + mem_chain +
 // mem_chain_flt): SMEMs of length >= min_seed_len on the FMD-index (both
 // strands at once), re-seeds inside long, rare SMEMs and the third-round
@@ -234,55 +294,7 @@ void chain_read(const KmerIndex& idx, const AlignOptions& opt, ReadAln& R, const
       chains.push_back(std::move(ch));
     }
   }
-  for (Chain& ch : chains) {  // bwa mem_chain_weight: query bases covered by the seeds (min with the reference's)
-    int64_t wq = 0, wr = 0, endq = 0, endr = 0;
-    for (const Seed& sd : ch.s) {
-      if (sd.qbeg >= endq) wq += sd.len;
-      else if (sd.qbeg + sd.len > endq) wq += sd.qbeg + sd.len - endq;
-      endq = std::max<int64_t>(endq, sd.qbeg + sd.len);
-    }
-    std::vector<const Seed*> byr;
-    for (const Seed& sd : ch.s) byr.push_back(&sd);
-    std::sort(byr.begin(), byr.end(), [](const Seed* a, const Seed* b) { return a->rbeg < b->rbeg; });
-    for (const Seed* sd : byr) {
-      if (sd->rbeg >= endr) wr += sd->len;
-      else if (sd->rbeg + sd->len > endr) wr += sd->rbeg + sd->len - endr;
-      endr = std::max<int64_t>(endr, sd->rbeg + sd->len);
-    }
-    ch.weight = (int)std::min(wq, wr);
-    const int b = ch.s.front().qbeg, e = ch.s.back().qbeg + ch.s.back().len;  // oriented
-    ch.qb = ch.rev ? L - e : b;
-    ch.qe = ch.rev ? L - b : e;
-  }
-  // ---- bwa mem_chain_flt
-  std::stable_sort(chains.begin(), chains.end(), [](const Chain& a, const Chain& b) { return a.weight > b.weight; });
-  std::vector<int> kept{0};
-  chains[0].kept = 3;
-  for (int i = 1; i < (int)chains.size(); ++i) {
-    bool large_ovlp = false;
-    size_t k = 0;
-    for (; k < kept.size(); ++k) {
-      Chain& cj = chains[kept[k]];
-      const Chain& ci = chains[i];
-      const int b_max = std::max(cj.qb, ci.qb), e_min = std::min(cj.qe, ci.qe);
-      if (e_min > b_max) {
-        const int li = ci.qe - ci.qb, lj = cj.qe - cj.qb, min_l = std::min(li, lj);
-        if (e_min - b_max >= min_l * opt.mask_level && min_l < opt.max_chain_gap) {
-          large_ovlp = true;
-          if (cj.first < 0) cj.first = i;
-          if (ci.weight < cj.weight * opt.drop_ratio && cj.weight - ci.weight >= opt.k << 1) break;
-        }
-      }
-    }
-    if (k == kept.size()) {
-      kept.push_back(i);
-      chains[i].kept = large_ovlp ? 2 : 3;
-    }
-  }
-  for (int j : kept)
-    if (chains[j].first >= 0) chains[chains[j].first].kept = 1;
-  for (Chain& ch : chains)
-    if (ch.kept > 0) R.chains.push_back(std::move(ch));
+  finish_chains(opt, R, chains);
 }
 
 void seed_read(const KmerIndex& idx, const AlignOptions& opt, ReadAln& R) {
@@ -291,6 +303,55 @@ void seed_read(const KmerIndex& idx, const AlignOptions& opt, ReadAln& R) {
   std::vector<BiInterval> mems;
   idx.fmd().collect(q.data(), (int)q.size(), P.min_len, P.split_len, P.split_width, P.max_mem_intv, mems);
   chain_read(idx, opt, R, mems.data(), mems.size(), nullptr);
+}
+
+// The minimizer seeder's chain_read: the read's n anchors (t, q) with the
+// recurrence's f and p (host or device) are backtracked into chains
+// (mm_backtrack); consecutive anchors of a chain on one diagonal whose k-mers
+// overlap or abut merge into one Seed (their union is an exact match); then
+// mem_chain_weight and mem_chain_flt as for SMEM chains.  text (nullable)
+// takes the read's --chains-out lines.
+void chain_read_minimizer(const AlignOptions& opt, ReadAln& R, const int64_t* t, const int32_t* q, const int32_t* f, const int32_t* p,
+                          int n, int64_t& n_chains, std::string* text) {
+  std::vector<MmChain> mc;
+  mm_backtrack(f, p, n, opt.mm.min_cnt, opt.mm.min_score, mc);
+  n_chains = (int64_t)mc.size();
+  if (text) {
+    std::string& o = *text;
+    o += "anchors " + std::to_string(n) + "\nf";
+    for (int i = 0; i < n; ++i) o += ' ' + std::to_string(f[i]);
+    o += "\np";
+    for (int i = 0; i < n; ++i) o += ' ' + std::to_string(p[i]);
+    o += '\n';
+    for (const MmChain& c : mc) {
+      o += "chain " + std::to_string(c.score) + ' ' + std::to_string(c.anchors.size());
+      for (int32_t a : c.anchors) o += ' ' + std::to_string(a);
+      o += '\n';
+    }
+  }
+  if (mc.empty()) return;
+  const int k = opt.mm.k;
+  std::vector<Chain> chains;
+  for (const MmChain& c : mc) {
+    Chain ch;
+    const int64_t t0 = t[c.anchors.front()];
+    ch.contig = fcs::mm_target_contig(t0), ch.rev = fcs::mm_target_rev(t0);
+    for (int32_t a : c.anchors) {
+      Seed sd;
+      sd.contig = ch.contig, sd.rev = ch.rev;
+      sd.qbeg = q[a] - k + 1, sd.len = k, sd.rbeg = fcs::mm_target_pos(t[a]) - k + 1;
+      if (!ch.s.empty()) {
+        Seed& last = ch.s.back();
+        if (sd.rbeg - sd.qbeg == last.rbeg - last.qbeg && sd.qbeg <= last.qbeg + last.len) {
+          last.len = sd.qbeg + sd.len - last.qbeg;
+          continue;
+        }
+      }
+      ch.s.push_back(sd);
+    }
+    chains.push_back(std::move(ch));
+  }
+  finish_chains(opt, R, chains);
 }
 
 // mem_chain2aln's test: is seed s (almost) inside a region already made? (then
@@ -1194,20 +1255,68 @@ void link_mate(std::vector<BamRecord>& recs, const BamRecord& mate_in, bool read
 
 // Seeds, chains, the GPU extension rounds and dedup / patch for a batch of
 // reads; regions sorted by score (mem_sort_dedup_patch's order).
+// Seeder::minimizer for a batch: anchors per read on the host threads, the
+// recurrence over the whole batch in one call (fcsmm_chain with
+// opt.gpu_chain, else mm_chain_host), then backtrack and chains per read.
+// pairs: the batch is n mates 1 then n mates 2, and --chains-out lists a pair's
+// mates together.
+void seed_batch_minimizer(const KmerIndex& idx, const AlignOptions& opt, std::vector<ReadAln>& reads, bool pairs, AlignStats& st) {
+  const size_t N = reads.size();
+  std::vector<std::vector<int64_t>> ts(N);
+  std::vector<std::vector<int32_t>> qs(N);
+  parallel_for(N, opt.threads, [&](size_t r) {
+    ReadAln& R = reads[r];
+    mm_read_anchors(idx.mm(), R.code[0].data(), (int)R.code[0].size(), opt.mm.max_occ, ts[r], qs[r], R.frac_rep);
+  });
+  std::vector<int64_t> off(N + 1, 0);
+  for (size_t r = 0; r < N; ++r) off[r + 1] = off[r] + (int64_t)ts[r].size();
+  if (off[N] > INT32_MAX) throw failedCommand("[E::fcs-genome align] more than 2^31 - 1 anchors in a chunk: lower bwa.chunk_size");
+  std::vector<int64_t> t((size_t)off[N]);
+  std::vector<int32_t> q((size_t)off[N]), f((size_t)off[N]), p((size_t)off[N]);
+  parallel_for(N, opt.threads, [&](size_t r) {
+    std::copy(ts[r].begin(), ts[r].end(), t.begin() + off[r]);
+    std::copy(qs[r].begin(), qs[r].end(), q.begin() + off[r]);
+  });
+  fcsmm_batch b{};
+  b.n_reads = (int64_t)N, b.n_anchors = off[N], b.t = t.data(), b.q = q.data(), b.read_off = off.data();
+  b.max_gap = opt.mm.max_gap, b.bw = opt.mm.bw, b.span = opt.mm.k;
+  const uint64_t tc = now_us();
+  if (opt.gpu_chain) gpu_chain_batch(opt.gpu, b, f.data(), p.data());
+  else mm_chain_host(b, opt.threads, f.data(), p.data());
+  st.mm_chain_seconds += (now_us() - tc) / 1e6;
+  std::vector<int64_t> kept(N, 0);
+  std::vector<std::string> text(opt.want_chains ? N : 0);
+  parallel_for(N, opt.threads, [&](size_t r) {
+    chain_read_minimizer(opt, reads[r], t.data() + off[r], q.data() + off[r], f.data() + off[r], p.data() + off[r],
+                         (int)(off[r + 1] - off[r]), kept[r], opt.want_chains ? &text[r] : nullptr);
+  });
+  st.mm_anchors += off[N];
+  for (int64_t k : kept) st.mm_chains += k;
+  if (opt.want_chains) {
+    const size_t n = pairs ? N / 2 : N;
+    for (size_t i = 0; i < n; ++i) {
+      st.chains_text += "read " + std::to_string(opt.read_id0 + (int64_t)i) + (pairs ? "/1 " : " ") + text[i];
+      if (pairs) st.chains_text += "read " + std::to_string(opt.read_id0 + (int64_t)i) + "/2 " + text[n + i];
+    }
+  }
+}
+
 void align_batch(const KmerIndex& idx, const std::vector<std::string>& seqs, const AlignOptions& opt,
-                 std::vector<ReadAln>& reads, AlignStats& st) {
+                 std::vector<ReadAln>& reads, AlignStats& st, bool pairs = false) {
   const uint64_t t0 = now_us();
   reads.assign(seqs.size(), ReadAln{});
+  const bool smem = opt.seeder == Seeder::smem;
   parallel_for(seqs.size(), opt.threads, [&](size_t r) {
     ReadAln& R = reads[r];
     R.seq[0] = seqs[r];
     R.seq[1] = revcomp(seqs[r]);
     R.code[0] = encode(R.seq[0]);
     R.code[1] = encode(R.seq[1]);
-    if (!opt.gpu_seed) seed_read(idx, opt, R);
+    if (smem && !opt.gpu_seed) seed_read(idx, opt, R);
   });
+  if (!smem && !reads.empty()) seed_batch_minimizer(idx, opt, reads, pairs, st);
   // one collect and one locate call for the chunk (fused: one call for both), then chaining per read
-  if (opt.gpu_seed && !reads.empty()) {
+  if (smem && opt.gpu_seed && !reads.empty()) {
     std::vector<const uint8_t*> q(reads.size());
     std::vector<int> qlen(reads.size());
     for (size_t r = 0; r < reads.size(); ++r) q[r] = reads[r].code[0].data(), qlen[r] = (int)reads[r].code[0].size();
@@ -1236,13 +1345,23 @@ void align_batch(const KmerIndex& idx, const std::vector<std::string>& seqs, con
 
 }  // namespace
 
-KmerIndex::KmerIndex(const Reference& ref, int k, const std::string& index_path) : k_(k) {
+Seeder seeder_from_name(const std::string& name) {
+  if (name == "smem") return Seeder::smem;
+  if (name == "minimizer") return Seeder::minimizer;
+  throw invalidParam("the seeder is smem or minimizer, not '" + name + "'");
+}
+
+KmerIndex::KmerIndex(const Reference& ref, int k, const std::string& index_path, const MmOptions* mm, int threads) : k_(k) {
   if (k < 8 || k > 63) throw invalidParam("minimum seed length must be in [8, 63]");
   for (const Contig& c : ref.contigs) {
     codes_.emplace_back(c.seq.size());
     for (size_t p = 0; p < c.seq.size(); ++p) codes_.back()[p] = code_of(c.seq[p]);
     off_.push_back(l_pac_);
     l_pac_ += (int64_t)c.seq.size();
+  }
+  if (mm) {
+    mm_ = std::make_unique<MmIndex>(codes_, mm->k, mm->w, threads);
+    return;
   }
   if (!index_path.empty()) fmd_ = FmdIndex::load(index_path, codes_);
   loaded_ = fmd_ != nullptr;
@@ -1309,7 +1428,7 @@ AlignStats align_pairs(const Reference& ref, const KmerIndex& idx, const std::ve
   std::vector<std::string> both(seqs1);
   both.insert(both.end(), seqs2.begin(), seqs2.end());
   std::vector<ReadAln> all;
-  align_batch(idx, both, opt, all, st);
+  align_batch(idx, both, opt, all, st, true);
   std::vector<ReadAln> m1(std::make_move_iterator(all.begin()), std::make_move_iterator(all.begin() + n));
   std::vector<ReadAln> m2(std::make_move_iterator(all.begin() + n), std::make_move_iterator(all.end()));
   all.clear();
@@ -1496,13 +1615,31 @@ class FastqReader {
 
 // The FMD-index of a reference, built once per process and shared by the
 // read-group jobs of one run (bwa-flow loads its prebuilt index per run).
-std::shared_ptr<const KmerIndex> index_cached(const std::string& path, const Reference& ref, int k) {
+// mm: the minimizer index of (k, w) in its place.
+std::shared_ptr<const KmerIndex> index_cached(const std::string& path, const Reference& ref, int k, const MmOptions* mm, int threads) {
   static std::mutex mu;
-  static std::map<std::pair<std::string, int>, std::shared_ptr<const KmerIndex>> cache;
+  static std::map<std::tuple<std::string, int, int, int>, std::shared_ptr<const KmerIndex>> cache;
   std::lock_guard<std::mutex> g(mu);
-  auto& e = cache[{path, k}];
-  if (!e) e = std::make_shared<const KmerIndex>(ref, k, fmd_index_path(path));
+  auto& e = cache[{path, k, mm ? mm->k : 0, mm ? mm->w : 0}];
+  if (!e) e = std::make_shared<const KmerIndex>(ref, k, fmd_index_path(path), mm, threads);
   return e;
+}
+
+// The minimap.* keys of the configuration.
+MmOptions mm_options_from_conf() {
+  MmOptions o;
+  o.k = conf().get_int("minimap.k"), o.w = conf().get_int("minimap.w"), o.max_occ = conf().get_int("minimap.max_occ");
+  o.max_gap = conf().get_int("minimap.max_gap"), o.bw = conf().get_int("minimap.bw");
+  o.min_cnt = conf().get_int("minimap.min_cnt"), o.min_score = conf().get_int("minimap.min_score");
+  mm_check_options(o);
+  return o;
+}
+
+bool env_true(const char* name) {
+  const char* v = std::getenv(name);
+  if (!v) return false;
+  const std::string s(v);
+  return s == "1" || s == "true" || s == "TRUE" || s == "on" || s == "yes";
 }
 
 void add_stats(AlignStats& tot, const AlignStats& st) {
@@ -1525,6 +1662,10 @@ void add_stats(AlignStats& tot, const AlignStats& st) {
   tot.seed_host_rows += st.seed_host_rows;
   tot.ext_tasks += st.ext_tasks;
   tot.global_tasks += st.global_tasks;
+  tot.mm_anchors += st.mm_anchors;
+  tot.mm_chains += st.mm_chains;
+  tot.mm_chain_seconds += st.mm_chain_seconds;
+  tot.chains_text += st.chains_text;
   if (st.pe_pairs) tot.pe_pairs = st.pe_pairs, tot.pe_low = st.pe_low, tot.pe_high = st.pe_high,
                    tot.pe_avg = st.pe_avg, tot.pe_std = st.pe_std;
 }
@@ -1549,7 +1690,23 @@ AlignStats align_fastq(const AlignJob& job, const std::vector<int>& devices, std
   AlignOptions base;
   base.rg = job.rg;
   base.chunk_size = conf().get_int("bwa.chunk_size");
-  const bool want_gpu_seed = conf().get_bool("bwa.gpu_seed");
+  base.seeder = seeder_from_name(job.seeder.empty() ? conf().get_string("bwa.seeder") : job.seeder);
+  const bool minimizer = base.seeder == Seeder::minimizer;
+  base.want_chains = !job.chains_out.empty();
+  if (base.want_chains && !minimizer) throw invalidParam("--chains-out needs the minimizer seeder (bwa.seeder)");
+  if (minimizer) {
+    base.mm = mm_options_from_conf();
+    const bool want = conf().get_bool("minimap.gpu_chain") || env_true("FCS_MINIMAP_GPU");
+    base.gpu_chain = want && gpu_chain_available();
+    if (want && !base.gpu_chain) {
+      static std::once_flag said;
+      std::call_once(said, [] {
+        std::fprintf(stderr, "[fcs-genome align] minimap.gpu_chain: the loaded libfcship has no fcsmm_chain entry point; "
+                             "chaining runs on the host\n");
+      });
+    }
+  }
+  const bool want_gpu_seed = !minimizer && conf().get_bool("bwa.gpu_seed");
   base.gpu_seed = want_gpu_seed && gpu_seed_available();
   base.gpu_seed_fused = base.gpu_seed && conf().get_bool("bwa.gpu_seed_fused") && gpu_seed_fused_available();
   if (want_gpu_seed && !base.gpu_seed) {
@@ -1567,7 +1724,8 @@ AlignStats align_fastq(const AlignJob& job, const std::vector<int>& devices, std
     base.threads = std::max(1, all / nslot);
   }
   const uint64_t t_ref = now_us();
-  const auto idx_p = index_cached(job.ref_path, ref, base.k);
+  const int all_threads = base.threads * nslot;
+  const auto idx_p = index_cached(job.ref_path, ref, base.k, minimizer ? &base.mm : nullptr, all_threads);
   const KmerIndex& idx = *idx_p;
   const uint64_t t_idx = now_us();
 
@@ -1756,6 +1914,11 @@ AlignStats align_fastq(const AlignJob& job, const std::vector<int>& devices, std
       for (const Interval& iv : buckets[k]) bed << iv.chrom << '\t' << iv.lb - 1 << '\t' << iv.ub << '\n';
     }
   }
+  if (base.want_chains) {
+    std::ofstream co(job.chains_out);
+    co << tot.chains_text;
+    if (!co.flush()) throw failedCommand("[E::fcs-genome align] cannot write " + job.chains_out);
+  }
   const uint64_t t_end = now_us();
   std::ostringstream rep;
   rep << "[fcs-genome align] " << tot.reads << " reads, " << tot.mapped << " mapped, " << tot.supplementary << " supplementary, " << tot.ext_tasks
@@ -1766,11 +1929,19 @@ AlignStats align_fastq(const AlignJob& job, const std::vector<int>& devices, std
         << tot.pe_avg << " +- " << tot.pe_std << " [" << tot.pe_low << ", " << tot.pe_high << "] from " << tot.pe_pairs
         << " pairs";
   rep << "\n[fcs-genome align] read group " << job.rg << " on " << nslot << " device slot(s), " << results.size()
-      << " chunks; phases: reference " << (t_ref - t_start) / 1e6 << " s, FMD index " << (t_idx - t_ref) / 1e6
-      << " s (" << (idx.loaded() ? "mapped " + fmd_index_path(job.ref_path) : std::string("built in memory")) << ", sa_intv "
-      << idx.fmd().sa_intv() << "), FASTQ + alignment " << (t_aln - t_idx) / 1e6 << " s (alignment thread-seconds " << tot.seconds
+      << " chunks; phases: reference " << (t_ref - t_start) / 1e6 << " s, ";
+  if (minimizer)
+    rep << "minimizer index " << (t_idx - t_ref) / 1e6 << " s (built in memory, " << idx.mm().size() << " minimizers, k " << base.mm.k
+        << ", w " << base.mm.w << ")";
+  else
+    rep << "FMD index " << (t_idx - t_ref) / 1e6 << " s (" << (idx.loaded() ? "mapped " + fmd_index_path(job.ref_path) : std::string("built in memory"))
+        << ", sa_intv " << idx.fmd().sa_intv() << ")";
+  rep << ", FASTQ + alignment " << (t_aln - t_idx) / 1e6 << " s (alignment thread-seconds " << tot.seconds
       << ": seeding " << tot.seed_seconds << ", extension " << tot.extend_seconds << ", pairing " << tot.pair_seconds
       << ", records " << tot.record_seconds << "), sort + BAM + index " << (t_end - t_aln) / 1e6 << " s\n";
+  if (minimizer)
+    rep << "[fcs-genome align] minimizer seeding (bwa.seeder): " << tot.mm_anchors << " anchors, " << tot.mm_chains
+        << " chains kept, chaining " << tot.mm_chain_seconds << " s " << (base.gpu_chain ? "(GPU)" : "(host)") << "\n";
   if (base.gpu_seed)
     rep << "[fcs-genome align] GPU seeding (bwa.gpu_seed): " << tot.seed_gpu_reads << " reads through the device, "
         << tot.seed_host_reads << " of them collected on the host (more than " << base.seed_max_mems << " SMEMs"

@@ -45,11 +45,23 @@
 #include "fmindex.h"
 #include "fcship.h"
 #include "gpu_seed.h"
+#include "minimizer.h"
 
 namespace fcsg {
 
+// What produces the Seeds and Chains of a read: SMEMs on the FMD-index (bwa
+// mem), or minimizer anchors chained by the recurrence of DESIGN §2 [EXT]
+// "minimizer seeding and chaining" (host/minimizer.h).  Everything from
+// mem_chain_flt on is the same.
+enum class Seeder { smem, minimizer };
+Seeder seeder_from_name(const std::string& name);  // "smem" | "minimizer"; throws invalidParam
+
 struct AlignOptions {
   int gpu = 0;
+  Seeder seeder = Seeder::smem;  // bwa.seeder
+  MmOptions mm;                  // the minimap.* keys (Seeder::minimizer)
+  bool gpu_chain = false;        // minimap.gpu_chain: the recurrence of a chunk in one fcsmm_chain call
+  bool want_chains = false;      // --chains-out: AlignStats::chains_text is filled
   int k = 19;            // minimum SMEM length (bwa -k min_seed_len)
   int max_occ = 500;     // occurrences kept per SMEM (bwa -c max_occ; sampled beyond)
   int w = 100;           // band width
@@ -85,16 +97,24 @@ struct AlignStats {
   // paired: the insert-size estimate of the (last) batch
   int pe_pairs = 0, pe_low = 0, pe_high = 0;
   double pe_avg = 0, pe_std = 0;
+  // Seeder::minimizer: anchors and kept chains of the batch, wall seconds of the recurrence
+  int64_t mm_anchors = 0, mm_chains = 0;
+  double mm_chain_seconds = 0;
+  std::string chains_text;  // --chains-out: per read (pairs: mate 1, mate 2) its anchors' f and p and its kept chains
   fcs_bsw_params params{};  // scoring of the batch (bwa defaults)
 };
 
 // The aligner's reference index: contigs as codes and their FMD-index
-// (host/fmindex.h) for SMEM seeding.
+// (host/fmindex.h) for SMEM seeding, or their minimizer index
+// (host/minimizer.h).
 class KmerIndex {
  public:
   // index_path: a saved FMD-index of `ref` (fcs-genome index) to map instead
-  // of building one; empty or unusable: built in memory
-  KmerIndex(const Reference& ref, int k, const std::string& index_path = "");
+  // of building one; empty or unusable: built in memory.  mm: the minimizer
+  // index is built in memory instead, and the FMD-index is neither built nor loaded.
+  KmerIndex(const Reference& ref, int k, const std::string& index_path = "", const MmOptions* mm = nullptr, int threads = 1);
+  bool has_fmd() const { return fmd_ != nullptr; }
+  const MmIndex& mm() const { return *mm_; }
   bool loaded() const { return loaded_; }  // the saved index was used
   int k() const { return k_; }  // minimum seed length (bwa -k)
   // the contig's bases as codes 0..4 (A, C, G, T, other)
@@ -119,6 +139,7 @@ class KmerIndex {
   std::unique_ptr<FmdIndex> fmd_;
   std::unique_ptr<TextMap> map_;
   std::unique_ptr<FmdDeviceCopies> dev_;  // after fmd_: destroyed first
+  std::unique_ptr<MmIndex> mm_;
 };
 
 // The saved FMD-index of a FASTA (fcs-genome index): <fasta>.fcsidx.
@@ -150,6 +171,8 @@ struct AlignJob {
   int bgzf_device = -1;        // >= 0: the BAM's blocks compress on that GPU (gpu.bgzf_deflate)
   bool disable_merge = false;  // bwa.num_buckets sorted bucket BAMs (+ .bai, .bed) in the directory `output`
   bool align_only = false;     // --align-only: no duplicate marking even with markdup.in_align
+  std::string seeder;          // empty: the key bwa.seeder
+  std::string chains_out;      // --chains-out: the text of AlignStats::chains_text, reads in input order
 };
 
 // Aligns one read group on the device slots `gpus`: FASTQ chunks

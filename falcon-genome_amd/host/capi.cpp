@@ -27,6 +27,7 @@
 #include "intervals.h"
 #include "joint.h"
 #include "markdup.h"
+#include "minimizer.h"
 #include "pileup.h"
 #include "sample_sheet.h"
 #include "vcf.h"
@@ -824,6 +825,65 @@ int fcsg_run_stage(const char* cmd_fmt, int n_tasks, int n_threads, const char* 
 
 int fcsg_find_error(const char* const* logs, int n, char* buf, int cap) {
   return copy_out(LogUtils::findError(std::vector<std::string>(logs, logs + n)), buf, cap);
+}
+
+// The host statement of minimizer seeding and chaining (minimizer.h).
+// fcsg_mm_sketch writes the minimizers of n codes (hash, position of the last
+// base, strand) and returns their number.  fcsg_mm_anchors builds the index of
+// n_contigs contigs (codes by offsets) and writes one read's anchors and
+// frac_rep.  fcsg_mm_chain is the recurrence's oracle over the arguments of
+// fcsmm_chain (include/fcsmm.h).  fcsg_mm_backtrack writes the kept chains of
+// one read: score[c] and the anchors anchors[chain_off[c] .. chain_off[c + 1]).
+// A count above cap is an error.
+int fcsg_mm_sketch(const uint8_t* codes, int64_t n, int k, int w, uint64_t* h, int32_t* pos, uint8_t* strand, int cap) {
+  int count = 0;
+  const int g = guard([&] {
+    std::vector<MmMini> m;
+    mm_sketch(codes, n, k, w, m);
+    if ((int64_t)m.size() > cap) throw invalidParam("fcsg_mm_sketch: more minimizers than cap");
+    for (size_t i = 0; i < m.size(); ++i) h[i] = m[i].h, pos[i] = m[i].pos, strand[i] = m[i].strand;
+    count = (int)m.size();
+  });
+  return g ? g : count;
+}
+
+int fcsg_mm_anchors(const uint8_t* ref, const int64_t* ref_off, int n_contigs, const uint8_t* read, int L, int k, int w, int max_occ,
+                    int64_t* t, int32_t* q, int cap, double* frac_rep) {
+  int count = 0;
+  const int g = guard([&] {
+    std::vector<std::vector<uint8_t>> contigs;
+    for (int c = 0; c < n_contigs; ++c) contigs.emplace_back(ref + ref_off[c], ref + ref_off[c + 1]);
+    const MmIndex idx(contigs, k, w);
+    std::vector<int64_t> tv;
+    std::vector<int32_t> qv;
+    mm_read_anchors(idx, read, L, max_occ, tv, qv, *frac_rep);
+    if ((int64_t)tv.size() > cap) throw invalidParam("fcsg_mm_anchors: more anchors than cap");
+    std::copy(tv.begin(), tv.end(), t), std::copy(qv.begin(), qv.end(), q);
+    count = (int)tv.size();
+  });
+  return g ? g : count;
+}
+
+int fcsg_mm_chain(const fcsmm_batch* b, int threads, int32_t* f, int32_t* p) {
+  return guard([&] { mm_chain_host(*b, threads, f, p); });
+}
+
+int fcsg_mm_backtrack(const int32_t* f, const int32_t* p, int n, int min_cnt, int min_score, int32_t* score, int32_t* chain_off,
+                      int32_t* anchors, int cap) {
+  int count = 0;
+  const int g = guard([&] {
+    std::vector<MmChain> ch;
+    mm_backtrack(f, p, n, min_cnt, min_score, ch);
+    if ((int64_t)ch.size() > cap) throw invalidParam("fcsg_mm_backtrack: more chains than cap");
+    int32_t at = 0;
+    for (size_t c = 0; c < ch.size(); ++c) {
+      score[c] = ch[c].score, chain_off[c] = at;
+      for (int32_t a : ch[c].anchors) anchors[at++] = a;
+    }
+    chain_off[ch.size()] = at;
+    count = (int)ch.size();
+  });
+  return g ? g : count;
 }
 
 }  // extern "C"

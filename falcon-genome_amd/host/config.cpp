@@ -36,6 +36,7 @@ void Config::init(const std::string& root_dir) {
   declare("bwa.nt", "-1", "host threads of the aligner (-1: all)");
   declare("bwa.num_buckets", "1024", "number of BAM buckets");
   declare("bwa.chunk_size", "100000", "reads per SW batch handed to the GPU");
+  declare("bwa.seeder", "smem", "the aligner's seeder: smem (FMD-index SMEMs) | minimizer (minimizer anchors, chained)");
   declare("bwa.gpu_seed", "false",
           "collect SMEMs and locate their occurrences on the GPU (one call each per chunk) instead of on the host threads");
   declare("bwa.gpu_seed_fused", "true",
@@ -90,6 +91,15 @@ void Config::init(const std::string& root_dir) {
   declare("joint.heterozygosity", "0.001", "joint: the allele-count prior's heterozygosity");
   declare("joint.max_alt", "6", "joint: ALTs kept per site, the most named first (at most 6)");
   declare("joint.chunk_sites", "0", "joint: sites per genotyping call (0: as many as return 2^24 PLs at most)");
+  declare("germline.seeder", "minimizer", "germline: the aligner's seeder (minimizer | smem)");
+  declare("minimap.k", "21", "minimizer seeding: k-mer length (4 to 31)");
+  declare("minimap.w", "11", "minimizer seeding: k-mers per window");
+  declare("minimap.max_occ", "500", "minimizer seeding: a minimizer with more occurrences yields no anchors");
+  declare("minimap.max_gap", "100", "minimizer chaining: the largest step between chained anchors, on the read and on the reference");
+  declare("minimap.bw", "50", "minimizer chaining: the largest diagonal step between chained anchors");
+  declare("minimap.min_cnt", "2", "minimizer chaining: anchors of a kept chain, at least");
+  declare("minimap.min_score", "20", "minimizer chaining: score of a kept chain, at least");
+  declare("minimap.gpu_chain", "false", "run the chaining recurrence of a chunk on the GPU (fcsmm_chain) instead of on the host threads");
   declare("indel.gpu", "false", "score (consensus, read) pairs on the GPU (fcsir_score) instead of on the host (indel)");
   declare("indel.chunk_pairs", "1048576", "indel: (consensus, read) pairs per scoring call (a bin is never split)");
   declare("indel.max_reads", "20000", "indel: a bin with more cleanable records is left untouched");

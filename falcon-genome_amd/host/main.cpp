@@ -203,6 +203,55 @@ void timeline(const char* what) {
   std::cerr << line << std::endl;
 }
 
+// What `htc` queues over one BAM (or directory of part BAMs): the shard tasks,
+// the concat to <output> + .gz + .tbi, and the warm-up and release workers.
+// `germline` runs the same stages over the BAM it aligned.
+struct HtcRun {
+  std::string ref, input, output, intervals, sample_id;
+  std::vector<std::string> extra;
+  bool force = false, produce_vcf = false, skip_concat = false;
+};
+
+void run_htc(const HtcRun& r, const std::vector<int>& gpus) {
+  const std::string &ref = r.ref, &input = r.input, &output = r.output, &sample_id = r.sample_id;
+  const std::vector<std::string>& extra = r.extra;
+  const bool force = r.force;
+  const std::string out_dir = conf().temp_dir() + "/htc";
+  create_dir(out_dir);
+  const bool flag_vcf = r.produce_vcf;
+  const auto shards = is_directory(input) ? dir_shards(r.intervals) : shard_intervals(ref, r.intervals);
+  timeline("shards");
+  // the GPU runtime and tables come up in the background while the first
+  // shards decode and pile up their reads (the reference's BackgroundExecutor
+  // NAM daemon runs beside its Executor the same way)
+  BackgroundExecutor warm("gpu-warmup", std::make_shared<DeviceWarmupWorker>(gpus));
+  Executor ex("Haplotype Caller", conf().get_int("gatk.htc.nprocs", "gatk.nprocs"), gpus);
+  std::vector<std::string> parts;
+  for (size_t k = 0; k < shards.size(); ++k) {
+    const std::string part = get_contig_fname(out_dir, (int)k, flag_vcf ? "vcf" : "g.vcf");
+    parts.push_back(part);
+    ex.addTask(std::make_shared<HTCWorker>(ref, shards[k], input, part, extra, (int)k, flag_vcf, true), sample_id);
+  }
+  const std::string plain = output;
+  if (!r.skip_concat) {
+    if (!force && path_exists(plain + ".gz")) throw invalidParam("output " + plain + ".gz exists (use -f)");
+    // concat -> bgzip -> tabix as one pass over the parts
+    ex.addTask(std::make_shared<VCFConcatWorker>(parts, plain, plain + ".gz", /*consume=*/true, bgzf_device(gpus)),
+               sample_id, true);
+  } else {
+    ex.addTask(std::make_shared<VCFConcatWorker>(parts, plain), sample_id, true);
+  }
+  // with gpu.bgzf_deflate the tail compresses on a device: the release waits for it (a stage of its own)
+  if (conf().get_bool("gpu.release_early"))
+    ex.addTask(std::make_shared<GpuReleaseWorker>(gpus, &warm), sample_id, bgzf_device(gpus) >= 0);
+  timeline("stages queued");
+  ex.run();
+  timeline("stages done");
+  warm.wait();
+  timeline("warm-up joined");
+  if (warm.status() != 0) throw failedCommand(std::string("[E::fcs-genome] GPU warm-up failed: ") + fcs_last_error());
+}
+
 int htc_main(int argc, char** argv) {
   Args a;
   common_opts(a);
@@ -221,47 +270,14 @@ int htc_main(int argc, char** argv) {
     std::cerr << "'fcs-genome htc' options:\n" << a.help();
     throw;
   }
-  const std::string ref = a.get("ref"), input = a.get("input"), output = a.get("output");
-  const bool force = a.has("force");
-  const std::string sample_id = a.get("sample-id");
-  std::vector<std::string> extra = a.all("extra-options");
-  if (a.has("dump-regions")) extra.push_back("--dump-regions " + a.get("dump-regions"));
-  const std::vector<int> gpus = slots();
-  const std::string out_dir = conf().temp_dir() + "/htc";
-  create_dir(out_dir);
-  const bool flag_vcf = a.has("produce-vcf");
+  HtcRun r;
+  r.ref = a.get("ref"), r.input = a.get("input"), r.output = a.get("output"), r.intervals = a.get("intervalList");
+  r.sample_id = a.get("sample-id");
+  r.extra = a.all("extra-options");
+  if (a.has("dump-regions")) r.extra.push_back("--dump-regions " + a.get("dump-regions"));
+  r.force = a.has("force"), r.produce_vcf = a.has("produce-vcf"), r.skip_concat = a.has("skip-concat");
   timeline("options parsed");
-  const auto shards = is_directory(input) ? dir_shards(a.get("intervalList")) : shard_intervals(ref, a.get("intervalList"));
-  timeline("shards");
-  // the GPU runtime and tables come up in the background while the first
-  // shards decode and pile up their reads (the reference's BackgroundExecutor
-  // NAM daemon runs beside its Executor the same way)
-  BackgroundExecutor warm("gpu-warmup", std::make_shared<DeviceWarmupWorker>(gpus));
-  Executor ex("Haplotype Caller", conf().get_int("gatk.htc.nprocs", "gatk.nprocs"), gpus);
-  std::vector<std::string> parts;
-  for (size_t k = 0; k < shards.size(); ++k) {
-    const std::string part = get_contig_fname(out_dir, (int)k, flag_vcf ? "vcf" : "g.vcf");
-    parts.push_back(part);
-    ex.addTask(std::make_shared<HTCWorker>(ref, shards[k], input, part, extra, (int)k, flag_vcf, true), sample_id);
-  }
-  const std::string plain = output;
-  if (!a.has("skip-concat")) {
-    if (!force && path_exists(plain + ".gz")) throw invalidParam("output " + plain + ".gz exists (use -f)");
-    // concat -> bgzip -> tabix as one pass over the parts
-    ex.addTask(std::make_shared<VCFConcatWorker>(parts, plain, plain + ".gz", /*consume=*/true, bgzf_device(gpus)),
-               sample_id, true);
-  } else {
-    ex.addTask(std::make_shared<VCFConcatWorker>(parts, plain), sample_id, true);
-  }
-  // with gpu.bgzf_deflate the tail compresses on a device: the release waits for it (a stage of its own)
-  if (conf().get_bool("gpu.release_early"))
-    ex.addTask(std::make_shared<GpuReleaseWorker>(gpus, &warm), sample_id, bgzf_device(gpus) >= 0);
-  timeline("stages queued");
-  ex.run();
-  timeline("stages done");
-  warm.wait();
-  timeline("warm-up joined");
-  if (warm.status() != 0) throw failedCommand(std::string("[E::fcs-genome] GPU warm-up failed: ") + fcs_last_error());
+  run_htc(r, slots());
   return 0;
 }
 
@@ -316,6 +332,58 @@ int mutect2_main(int argc, char** argv) {
   return 0;
 }
 
+// One sample of `align` or `germline`: a BWAWorker per read group, each in its
+// own stage and on every GPU slot, and a merge stage when there are several.
+struct AlignRun {
+  std::string ref;
+  std::vector<std::string> extra;
+  bool force = false, disable_merge = false, align_only = false;
+  std::string seeder;      // empty: the key bwa.seeder
+  std::string chains_out;  // --chains-out; with a sample sheet .<sample>, with several read groups .<read group> is appended
+};
+
+void align_sample(const AlignRun& r, const std::string& sample_id, const std::vector<SampleDetails>& list, const std::string& merged,
+                  bool from_sheet, const std::vector<int>& gpus) {
+  const std::string temp_dir = conf().temp_dir() + "/align";
+  create_dir(temp_dir);
+  // one Executor per sample (the reference runs it inside the sample loop);
+  // one task at a time, each task on every GPU slot
+  Executor ex("align", 1, gpus);
+  const std::string merge_dir = temp_dir + "/" + sample_id + "merge";
+  create_dir(merge_dir);
+  std::vector<std::string> rg_out;
+  for (const SampleDetails& d : list) {
+    const std::string out_rg = list.size() == 1 ? merged : merge_dir + "/" + sample_id + "_" + d.ReadGroup + ".bam";
+    // two read groups of one sample writing one BAM would lose one lane and
+    // merge the other twice, silently
+    if (std::find(rg_out.begin(), rg_out.end(), out_rg) != rg_out.end())
+      throw invalidParam("sample " + sample_id + " lists read group " + d.ReadGroup +
+                         " more than once (each read group is aligned to its own BAM)");
+    rg_out.push_back(out_rg);
+    auto w = std::make_shared<BWAWorker>(r.ref, d.fastqR1, d.fastqR2, out_rg, r.extra, sample_id, d.ReadGroup, d.Platform,
+                                         d.LibraryID, !r.disable_merge, r.force || list.size() > 1, gpus, r.align_only);
+    std::string chains = r.chains_out;
+    if (!chains.empty() && from_sheet) chains += "." + sample_id;
+    if (!chains.empty() && list.size() > 1) chains += "." + d.ReadGroup;
+    w->set_seeding(r.seeder, chains);
+    ex.addTask(w, sample_id, true);
+  }
+  if (list.size() > 1) {
+    if (!r.disable_merge) {
+      ex.addTask(std::make_shared<MergeBamWorker>(rg_out, merged, r.force), sample_id, true);
+    } else {  // bucket i of every read group -> bucket i of the sample (worker-align.cpp:226-246)
+      create_dir(merged);
+      const int nb = std::max(1, conf().get_int("bwa.num_buckets"));
+      for (int i = 0; i < nb; ++i) {
+        std::vector<std::string> in;
+        for (const std::string& rg : rg_out) in.push_back(get_contig_fname(rg, i, "bam"));
+        ex.addTask(std::make_shared<MergeBamWorker>(in, get_contig_fname(merged, i, "bam"), true), sample_id, i == 0);
+      }
+    }
+  }
+  ex.run();
+}
+
 // `fcs-genome align` (reference src/worker-align.cpp:19-256): a single read
 // group (-1/-2, -R/-S/-P/-L) or a sample sheet (-F; file or FASTQ folder).
 // One BWAWorker per (sample, read group), each in its own stage and on every
@@ -339,6 +407,7 @@ int align_main(int argc, char** argv) {
   a.add("lb", "L", false, false, "library id ('LB' in BAM header)");
   a.add("align-only", "l", true, false, "skip mark duplicates (they are marked only with markdup.in_align=true)");
   a.add("disable-merge", "", true, false, "give bucket bams instead of the whole bam");
+  a.add("chains-out", "", false, false, "debug (bwa.seeder=minimizer): write every read's chaining scores, predecessors and kept chains");
   try {
     a.parse(argc, argv);
   } catch (helpRequest&) {
@@ -372,45 +441,105 @@ int align_main(int argc, char** argv) {
       throw fileNotFound("Output path " + output + " is not a directory");
     create_dir(output);
   }
+  AlignRun r;
+  r.ref = ref, r.extra = extra, r.force = force, r.disable_merge = disable_merge, r.align_only = align_only;
+  r.chains_out = a.get("chains-out");
   const std::vector<int> gpus = slots();
-  const std::string temp_dir = conf().temp_dir() + "/align";
-  create_dir(temp_dir);
+  for (const auto& [sample_id, list] : samples)
+    align_sample(r, sample_id, list, sheet.empty() ? output : output + "/" + sample_id + ".bam", !sheet.empty(), gpus);
+  return 0;
+}
+
+// `fcs-genome germline` (reference src/worker-germline.cpp): FASTQ to GVCF in
+// one run.  Per sample: every read group aligned with the minimizer seeder
+// (germline.seeder; the reference's minimap-flow), several merged; then the
+// stages of `htc` over that BAM.  The BAM stays (<output>.bam) with
+// --produce-bam, otherwise it lives under the temp dir.  With -F the outputs
+// are <output>/<sample>.{vcf,bam}.  The reference's bucket-BAM hand-off between
+// the halves is not restated: htc reads the one sorted BAM.
+int germline_main(int argc, char** argv) {
+  Args a;
+  common_opts(a);
+  a.add("ref", "r", false, true, "reference genome path");
+  a.add("fastq1", "1", false, false, "input pair-end fastq file (plain or .gz)");
+  a.add("fastq2", "2", false, false, "input pair-end fastq file (plain or .gz)");
+  a.add("sample_sheet", "F", false, false, "sample sheet or folder");
+  a.add("read-group", "R", false, false, "read group id ('ID' in BAM header)");
+  a.add("sample-id", "S", false, false, "sample id ('SM' in BAM header)");
+  a.add("platform", "P", false, false, "platform id ('PL' in BAM header)");
+  a.add("library", "l", false, false, "library id ('LB' in BAM header)");
+  a.add("produce-bam", "b", true, false, "keep the sorted BAM (the output with extension .bam)");
+  a.add("output", "o", false, true, "output GVCF/VCF file (<output>.gz + .tbi are written too; with --sample_sheet a folder)");
+  a.add("produce-vcf", "v", true, false, "produce VCF instead of GVCF");
+  a.add("intervalList", "L", false, false, "interval list file");
+  a.add("gatk4", "", true, false, "accepted for compatibility");
+  a.add("htc-extra-options", "", false, false, "extra options for HaplotypeCaller");
+  a.add("chains-out", "", false, false, "debug: write every read's chaining scores, predecessors and kept chains");
+  try {
+    a.parse(argc, argv);
+  } catch (helpRequest&) {
+    std::cerr << "'fcs-genome germline' options:\n" << a.help();
+    throw;
+  }
+  const std::string ref = a.get("ref"), sheet = a.get("sample_sheet"), fq1 = a.get("fastq1"), fq2 = a.get("fastq2");
+  const std::string output = a.get("output");
+  const bool force = a.has("force"), keep_bam = a.has("produce-bam");
+  SampleSheetMap samples;
+  if (sheet.empty()) {
+    if (fq1.empty() || fq2.empty()) throw invalidParam("Either --sample_sheet or --fastq1,fastq2 needs to be specified");
+    SampleDetails d;
+    d.fastqR1 = fq1, d.fastqR2 = fq2;
+    d.ReadGroup = a.get("read-group", "sample"), d.Platform = a.get("platform", "illumina"), d.LibraryID = a.get("library", "sample");
+    samples[a.get("sample-id", "sample")].push_back(d);
+  } else {
+    if (!fq1.empty() || !fq2.empty())
+      throw invalidParam("--sample_sheet and --fastq1,fastq2 cannot be specified at the same time");
+    samples = read_sample_sheet(sheet);
+  }
+  if (!is_regular_file(ref)) throw fileNotFound(ref);
+  if (!sheet.empty()) {
+    if (path_exists(output) && !is_directory(output)) throw fileNotFound("Output path " + output + " is not a directory");
+    create_dir(output);
+  }
+  // <stem>.<ext> of one sample's output
+  auto with_ext = [](const std::string& path, const std::string& ext) {
+    const size_t dot = path.find_last_of('.'), slash = path.find_last_of('/');
+    const bool has = dot != std::string::npos && (slash == std::string::npos || dot > slash + 1);
+    return (has ? path.substr(0, dot) : path) + "." + ext;
+  };
+  const bool flag_vcf = a.has("produce-vcf");
+  struct Out {
+    std::string vcf, bam;
+  };
+  std::map<std::string, Out> outs;
+  const std::string bam_dir = conf().temp_dir() + "/germline";
+  for (const auto& kv : samples) {
+    Out o;
+    o.vcf = sheet.empty() ? output : output + "/" + kv.first + (flag_vcf ? ".vcf" : ".g.vcf");
+    o.bam = keep_bam ? with_ext(o.vcf, "bam") : bam_dir + "/" + kv.first + ".bam";
+    if (!force)
+      for (const std::string& f : {o.vcf, o.vcf + ".gz", keep_bam ? o.bam : std::string()})
+        if (!f.empty() && path_exists(f)) throw invalidParam("output " + f + " exists (use -f)");
+    outs[kv.first] = o;
+  }
+  if (!keep_bam) create_dir(bam_dir);
+  AlignRun r;
+  r.ref = ref, r.extra = a.all("extra-options"), r.force = force || !keep_bam;
+  r.seeder = conf().get_string("germline.seeder"), r.chains_out = a.get("chains-out");
+  seeder_from_name(r.seeder);
+  const std::vector<int> gpus = slots();
   for (const auto& [sample_id, list] : samples) {
-    // one Executor per sample (the reference runs it inside the sample loop);
-    // one task at a time, each task on every GPU slot
-    Executor ex("align", 1, gpus);
-    const std::string merge_dir = temp_dir + "/" + sample_id + "merge";
-    create_dir(merge_dir);
-    const std::string merged = sheet.empty() ? output : output + "/" + sample_id + ".bam";
-    std::vector<std::string> rg_out;
-    for (const SampleDetails& d : list) {
-      const std::string out_rg = list.size() == 1 ? merged : merge_dir + "/" + sample_id + "_" + d.ReadGroup + ".bam";
-      // two read groups of one sample writing one BAM would lose one lane and
-      // merge the other twice, silently
-      if (std::find(rg_out.begin(), rg_out.end(), out_rg) != rg_out.end())
-        throw invalidParam("sample " + sample_id + " lists read group " + d.ReadGroup +
-                           " more than once (each read group is aligned to its own BAM)");
-      rg_out.push_back(out_rg);
-      ex.addTask(std::make_shared<BWAWorker>(ref, d.fastqR1, d.fastqR2, out_rg, extra, sample_id, d.ReadGroup,
-                                             d.Platform, d.LibraryID, !disable_merge, force || list.size() > 1, gpus,
-                                             align_only),
-                 sample_id, true);
+    const Out& o = outs[sample_id];
+    align_sample(r, sample_id, list, o.bam, !sheet.empty(), gpus);
+    HtcRun h;
+    h.ref = ref, h.input = o.bam, h.output = o.vcf, h.intervals = a.get("intervalList"), h.sample_id = sample_id;
+    h.extra = a.all("htc-extra-options");
+    h.force = force, h.produce_vcf = flag_vcf;
+    run_htc(h, gpus);
+    if (!keep_bam) {
+      std::remove(o.bam.c_str());
+      std::remove((o.bam + ".bai").c_str());
     }
-    if (list.size() > 1) {
-      if (!disable_merge) {
-        ex.addTask(std::make_shared<MergeBamWorker>(rg_out, merged, force), sample_id, true);
-      } else {  // bucket i of every read group -> bucket i of the sample (worker-align.cpp:226-246)
-        create_dir(merged);
-        const int nb = std::max(1, conf().get_int("bwa.num_buckets"));
-        for (int i = 0; i < nb; ++i) {
-          std::vector<std::string> in;
-          for (const std::string& r : rg_out) in.push_back(get_contig_fname(r, i, "bam"));
-          ex.addTask(std::make_shared<MergeBamWorker>(in, get_contig_fname(merged, i, "bam"), true), sample_id,
-                     i == 0);
-        }
-      }
-    }
-    ex.run();
   }
   return 0;
 }
@@ -811,6 +940,7 @@ int print_help() {
   std::cout << "Falcon Genome Analysis Toolkit (MI355X / gfx950 build)\n"
                "Usage: fcs-genome [command] <options>\n\nCommands:\n"
                "  align           align FASTQ reads into a sorted BAM (GPU banded SW)\n"
+               "  germline        FASTQ to GVCF in one run: minimizer-seeded align, then htc\n"
                "  markdup         mark duplicate reads of a BAM (GPU sort + segmented arg-max)\n"
                "  indel           indel realignment of a BAM, IndelRealigner-style (GPU consensus scoring)\n"
                "  baserecal       base recalibration table of a BAM against known sites (GPU covariate counting)\n"
@@ -858,6 +988,7 @@ int main(int argc, char** argv) {
     if (cmd == "htc") ret = htc_main(argc - 1, argv + 1);
     else if (cmd == "mutect2") ret = mutect2_main(argc - 1, argv + 1);
     else if (cmd == "align" || cmd == "al") ret = align_main(argc - 1, argv + 1);
+    else if (cmd == "germline" || cmd == "gm") ret = germline_main(argc - 1, argv + 1);
     else if (cmd == "markdup" || cmd == "md") ret = markdup_main(argc - 1, argv + 1);
     else if (cmd == "baserecal") ret = bqsr_main(argc - 1, argv + 1, BqsrCommand::kBaserecal);
     else if (cmd == "printreads" || cmd == "pr") ret = bqsr_main(argc - 1, argv + 1, BqsrCommand::kPrintreads);

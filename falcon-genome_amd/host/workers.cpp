@@ -283,6 +283,8 @@ int BWAWorker::run(TaskContext& ctx) {
   job.library = library_id_;
   job.disable_merge = !flag_merge_bams_;
   job.align_only = flag_align_only_;
+  job.seeder = seeder_;
+  job.chains_out = chains_out_;
   if (conf().get_bool("gpu.bgzf_deflate"))
     for (int d : gpus_)
       if (d >= 0 && job.bgzf_device < 0) job.bgzf_device = d;

@@ -111,11 +111,14 @@ class BWAWorker : public Worker {
             std::vector<std::string> extra_opts, std::string sample_id, std::string read_group,
             std::string platform_id, std::string library_id, bool flag_merge_bams, bool flag_f,
             std::vector<int> gpus, bool flag_align_only = false);
+  // seeder: empty for the key bwa.seeder; chains_out: --chains-out's file, or empty
+  void set_seeding(std::string seeder, std::string chains_out) { seeder_ = std::move(seeder), chains_out_ = std::move(chains_out); }
   void check() override;
   int run(TaskContext& ctx) override;
 
  private:
   std::string ref_path_, fq1_path_, fq2_path_, output_path_, sample_id_, read_group_, platform_id_, library_id_;
+  std::string seeder_, chains_out_;
   bool flag_merge_bams_, flag_f_, flag_align_only_ = false;
   std::vector<int> gpus_;
 };
