@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <string>
 
 #include "bsw_scan.h"
@@ -43,6 +44,17 @@ constexpr int kKswXByte = 0x10000, kKswXStop = 0x20000, kKswXSubo = 0x40000, kKs
 constexpr int kBlockBig = 1 << 20;  // > the range of one block's scan values; block ids < 16
 constexpr int kAlignSegQ = 160;                // longest query of the 16-lane groups (NK = 10 slots)
 constexpr long long kAlignGridCap = 1 << 20;  // workgroups per launch (they stride beyond)
+
+// FCSHIP_ALIGN_GRID=n (tests), read once; <= 0: ignored.  Lowers the cap so
+// that a test-sized batch's workgroups make many trips of the task loop
+// (2^20 workgroups need more than 1M / 4M tasks); never raises it.
+static long long align_grid_cap() {
+  static const long long forced = [] {
+    const char* e = std::getenv("FCSHIP_ALIGN_GRID");
+    return e ? std::atoll(e) : 0ll;
+  }();
+  return forced > 0 ? std::min(forced, kAlignGridCap) : kAlignGridCap;
+}
 
 // Group-level primitives: W = 16 (a DPP row) or 64 (the wave).
 template <int W>
@@ -556,7 +568,7 @@ int launch_bsw_align(const BswDevBatch& b, const BswParams& p, const int32_t* xt
   const bool packed16 = packed && align_packed_ok(align_i16_mmax(max_mat), 8, p.o_ins, p.e_ins);
   // one workgroup per four tasks (per task for W = 64): the dispatcher
   // balances the uneven task lengths and early exits
-  const unsigned grid16 = (unsigned)std::min<long long>((b.n + 3) / 4, kAlignGridCap);
+  const unsigned grid16 = (unsigned)std::min<long long>((b.n + 3) / 4, align_grid_cap());
   if (packed)
     rc = go((const void*)bsw_align_kernel<16, 10, true>, grid16, lds16, [&](unsigned grid, size_t lds) {
       hipLaunchKernelGGL((bsw_align_kernel<16, 10, true>), dim3(grid), dim3(64), lds, s, b, p, xtra, out, mt, seg_q,
@@ -568,7 +580,7 @@ int launch_bsw_align(const BswDevBatch& b, const BswParams& p, const int32_t* xt
                          packed ? 2 : 0);
     });
   if (rc == FCS_OK && max_qlen > seg_q) {
-    const unsigned grid = (unsigned)std::min<long long>(b.n, kAlignGridCap);
+    const unsigned grid = (unsigned)std::min<long long>(b.n, align_grid_cap());
     // slots of 64 positions for slen * p (p = 16 u8 / 8 i16: at most qlen + 15)
     if (max_qlen + 15 <= 256)
       rc = go((const void*)bsw_align_kernel<64, 4, false>, grid, lds64, [&](unsigned g, size_t lds) {

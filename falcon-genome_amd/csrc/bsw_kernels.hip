@@ -24,6 +24,12 @@
 
 namespace fcs {
 
+// Workgroup caps of the two wave-per-task launches (the tests read them): the
+// wide-bucket extension takes one task per workgroup and trip, the global
+// kernel one 64-task probe.
+constexpr long long kExtendWideGrid = 2048;
+constexpr long long kGlobalGrid = 2048;
+
 template <int NS>
 __device__ void extend_task(const BswDevBatch& b, const BswParams& p, long long task, uint8_t* __restrict__ tl,
                             int32_t* __restrict__ res, int64_t* __restrict__ cells_out) {
@@ -216,8 +222,7 @@ int launch_bsw_extend_wide(const BswDevBatch& b, const BswParams& p, int max_qle
   // grid-stride over the sorted tail; 2048 waves (2 per SIMD) fill the chip,
   // and an empty tail (the common bwa case) costs only that many exits
   long long grid = b.n;
-  const long long cap = 2048;
-  if (grid > cap) grid = cap;
+  if (grid > kExtendWideGrid) grid = kExtendWideGrid;
   if (max_qlen <= 255)
     hipLaunchKernelGGL(bsw_extend_kernel<4>, dim3((unsigned)grid), dim3(64), lds, s, b, p, res, cells, order, bounds);
   else
@@ -978,8 +983,7 @@ int launch_bsw_global(const BswDevBatch& b, const BswParams& p, int max_qlen, in
   // grid-stride over the sorted tail; 2048 waves (2 per SIMD) fill the chip,
   // and an empty tail (the common bwa case) costs only that many exits
   long long grid = (b.n + 63) / 64;  // one 64-task probe per wave and round
-  const long long cap = 2048;
-  if (grid > cap) grid = cap;
+  if (grid > kGlobalGrid) grid = kGlobalGrid;
   // narrow bands: one lane per task (64 consecutive tasks per wave)
   const long long lane_waves = (b.n + 63) / 64;
   if (lane_waves > 0x7FFFFFFFLL) return fail(FCS_ERR_UNSUPPORTED, "[E::fcship] ksw_global2: batch too large");

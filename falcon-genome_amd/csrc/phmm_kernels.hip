@@ -577,6 +577,17 @@ int launch_phmm_bin_schedule(const PhmmDevBatch& b, int32_t* idx_out, int64_t* b
 
 constexpr size_t kLdsBytes = 160 * 1024;
 
+// Workgroup caps of the forward and rescue launches; past its cap a launch's
+// workgroups stride over the class.  One name per role (the tests read them):
+// the streamed and column kernels' batches, launch_one's groups, the fallback
+// pass over the handed-back list, the 64-lane rescue's waves (one pair each)
+// and the 16-lane rescue's four-pair groups.
+constexpr long long kStreamGridCap = 65536;
+constexpr long long kOneGridCap = 65536;
+constexpr long long kFallbackGroups = 2048;
+constexpr long long kRescueWaves = 4096;
+constexpr long long kRescueGroups = 2048;
+
 template <typename T, bool EXACT, bool RESCUE, int W = 16>
 static int launch_one(const PhmmDevBatch& b, const int32_t* order, const unsigned long long* count_dev,
                       long long count_host, const int64_t* bounds, int cls, int nslot, long long max_groups,
@@ -604,8 +615,7 @@ static int launch_one(const PhmmDevBatch& b, const int32_t* order, const unsigne
   // longest-first order and the tail is one group deep.  A 16K cap (each
   // workgroup striding over ~3 groups) measured 4% slower on C2
   // (gpurun_out/p5); the surplus workgroups of a class exit at once.
-  const long long cap = 65536;
-  if (grid > cap) grid = cap;
+  if (grid > kOneGridCap) grid = kOneGridCap;
   if (grid < 1) grid = 1;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64), lds, s, b, order, count_dev, count_host, bounds, cls, nslot,
                      tab, out, rescue_list, rescue_count, thr, use_rescue ? 1 : 0, nseg);
@@ -740,7 +750,7 @@ int launch_phmm_forward(const PhmmDevBatch& b, const int32_t* order, int64_t cou
     // chip's wave slots (256 CUs x 4 SIMDs x w), so the launch ends on short waves
     const int tail = 2 * 4 * 1024 * w;
     const unsigned grid = (unsigned)std::min<long long>(
-        std::max<long long>((count + 4 * K - 1) / (4 * K) + (tail + 3) / 4, 1), 65536);
+        std::max<long long>((count + 4 * K - 1) / (4 * K) + (tail + 3) / 4, 1), kStreamGridCap);
     auto launch = [&](auto kern) -> int {
       if (lds > 64 * 1024)
         FCS_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -799,7 +809,7 @@ int launch_phmm_forward(const PhmmDevBatch& b, const int32_t* order, int64_t cou
       // chip's wave slots (256 CUs x 4 SIMDs x w waves x 4 streams)
       const int tail = cols1_forced_k() ? 4 : 1024 * cols1_waves(cols_C(c)) * 4;
       const unsigned grid = (unsigned)std::min<long long>(
-          std::max<long long>((count + 4 * K - 1) / (4 * K) + (tail + 3) / 4, 1), 65536);
+          std::max<long long>((count + 4 * K - 1) / (4 * K) + (tail + 3) / 4, 1), kStreamGridCap);
       auto launch = [&](auto kern) -> int {
         hipLaunchKernelGGL(kern, dim3(grid), dim3(64), (size_t)kCols1Lds, st, b, order, bounds, j, K, tail, t.tf, out,
                            rescue_list, rescue_count, thr, use_rescue ? 1 : 0, fb_list, fb_count);
@@ -826,7 +836,7 @@ int launch_phmm_forward(const PhmmDevBatch& b, const int32_t* order, int64_t cou
     // chip's wave slots (256 CUs x 4 SIMDs x 3 waves x 8 half-streams)
     const int tail = 1024 * 3 * 8;
     const unsigned grid = (unsigned)std::min<long long>(
-        std::max<long long>((count + 8 * K - 1) / (8 * K) + (tail + 7) / 8, 1), 65536);
+        std::max<long long>((count + 8 * K - 1) / (8 * K) + (tail + 7) / 8, 1), kStreamGridCap);
     auto launch = [&](auto kern) -> int {
       hipLaunchKernelGGL(kern, dim3(grid), dim3(64), (size_t)kColsLds, st, b, order, bounds, j, K, tail, t.tf, out,
                          rescue_list, rescue_count, thr, use_rescue ? 1 : 0, fb_list, fb_count);
@@ -886,7 +896,7 @@ int launch_phmm_forward(const PhmmDevBatch& b, const int32_t* order, int64_t cou
   // Pairs the streamed kernel handed back (device-side list): the one-row
   // kernel with GKL's byte compare, appending to the same rescue list.
   return launch_one<float, false, false>(b, fb_list, fb_count, 0, nullptr, 0, ns_max,
-                                         std::min<long long>(groups, 2048), t.tf, out, rescue_list, rescue_count, thr,
+                                         std::min<long long>(groups, kFallbackGroups), t.tf, out, rescue_list, rescue_count, thr,
                                          use_rescue, s);
 }
 
@@ -901,7 +911,7 @@ int launch_phmm_rescue(const PhmmDevBatch& b, const int32_t* list, const unsigne
   // trip).  Haplotypes too long for a 64-lane ring take the 16-lane kernel.
   const int ns64 = nslot_for_w(max_hap_len, 64);
   if ((size_t)ring_stride<double>(ns64) + ns64 <= kLdsBytes) {
-    const long long g64 = std::min<long long>(max_count, 4096);
+    const long long g64 = std::min<long long>(max_count, kRescueWaves);
     if (exact)
       return launch_one<double, true, true, 64>(b, list, count_dev, 0, nullptr, 0, ns64, g64, t.td, out, nullptr,
                                                 nullptr, 0.f, false, s);
@@ -909,7 +919,7 @@ int launch_phmm_rescue(const PhmmDevBatch& b, const int32_t* list, const unsigne
                                                nullptr, 0.f, false, s);
   }
   long long groups = (max_count + 3) / 4;
-  if (groups > 2048) groups = 2048;
+  if (groups > kRescueGroups) groups = kRescueGroups;
   if (exact)
     return launch_one<double, true, true>(b, list, count_dev, 0, nullptr, 0, nslot_for(max_hap_len), groups, t.td, out,
                                           nullptr, nullptr, 0.f, false, s);

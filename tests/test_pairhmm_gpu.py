@@ -61,6 +61,13 @@ def random_batch(seed, n_reads, n_haps, rlo, rhi, hlo, hhi, n_frac=0.01, related
 
 def check_parity(p, gpu_out, exact):
     ref, used_d = oracle_lib.phmm_batch(p)
+    return compare_parity(gpu_out, ref, used_d, exact)
+
+
+def compare_parity(gpu_out, ref, used_d, exact):
+    """check_parity's comparison against an oracle answer computed beforehand
+    (ref, used_d as oracle_lib.phmm_batch returns them, one entry per pair)."""
+    assert gpu_out.shape == ref.shape == used_d.shape
     assert np.all(np.isfinite(gpu_out) == np.isfinite(ref)), "finite mask differs"
     fin = np.isfinite(ref)
     g, r = gpu_out[fin], ref[fin]
